@@ -12,8 +12,10 @@ One "step" = one whole job = for every layer: RoPE -> KV append -> split-head at
 streaming-pool update, for every prefill chunk and every decode token.  Inputs are synthetic
 N(0,1) bf16 q/k/v already resident in HBM (the q/k/v projections and MLP are hipBLASLt GEMMs
 outside the path).  `value` = (prefill tokens + decode tokens) / job time; prefill tok/s and
-decode tok/s are reported next to it, as is the same job with every head a retrieval head
-("full attention").
+decode tok/s are reported next to it.  A plain run sets up, warms up, times --steps jobs and prints
+the line; --full adds every other leg: the same job with every head a retrieval head ("full
+attention"), the CPU baseline, kernel rooflines, live parity, INT4, token-row linears, the whole
+model.  --dump-outputs DIR writes a fixed sample of the last timed job's outputs (OutputSample).
 
 Multi-GPU (--gpus N under torch.distributed.run): the 32 layers are sharded contiguously over
 N ranks (strong scaling), prefill chunks are pipelined through the stages with RCCL send/recv of
@@ -115,6 +117,11 @@ class HotPath:
         self.hidden_c = torch.zeros(1, chunk, HIDDEN, device=device, dtype=torch.bfloat16)
         self.hidden_1 = torch.zeros(1, 1, HIDDEN, device=device, dtype=torch.bfloat16)
         self.chunks = [(s, min(chunk, ctx - s)) for s in range(0, ctx, chunk)]
+        self.dump = None        # (--dump-outputs: an OutputSample that sees every launch's output of one job)
+
+    def _keep(self, kind, i, j, o):
+        if self.dump is not None:
+            self.dump.add(kind, i, j, o)
 
     def free(self):
         self.cache = None
@@ -168,12 +175,14 @@ class HotPath:
                     mine[j].record(s)
                     if keep is not None:
                         keep.append(o)
+                    self._keep("prefill", i, li, o)
             return x if x is not None else self.hidden_c[:, :n]
         for li in self._layers(ps):
             o = duo_static_attention_row_block(self.q_c[:, r0:r0 + n], self.k_c[:, r0:r0 + n], self.v_c[:, r0:r0 + n],
                                                self.cache, li, r0, c, ROPE_SCALE, ROPE_THETA)
             if keep is not None:
                 keep.append(o)
+            self._keep("prefill", i, li, o)
         return x if x is not None else self.hidden_c[:, :n]
 
     def prefill_stage(self, i, x, ps=None):
@@ -199,17 +208,65 @@ class HotPath:
                     mine[j].record(st)
                     if getattr(self, "keep_outputs", None) is not None:
                         self.keep_outputs.append(o)
+                    self._keep("prefill", i, li, o)
             return x if x is not None else self.hidden_c[:, :c]
         for li in self._layers(ps):
-            self.layer_core(li, c, s, self.q_c, self.k_c, self.v_c)
+            self._keep("prefill", i, li, self.layer_core(li, c, s, self.q_c, self.k_c, self.v_c))
         return x if x is not None else self.hidden_c[:, :c]
 
     def decode_stage(self, i, x, ps=None):
         for li in self._layers(ps):
-            self.layer_core(li, 1, self.ctx, self.q_1, self.k_1, self.v_1)
+            self._keep("decode", i, li, self.layer_core(li, 1, self.ctx, self.q_1, self.k_1, self.v_1))
         if ps is None or ps == len(self.pass_layers) - 1:
             self.cache.evict_last(1)   # reference benchmark_static.py:104 (once per token: behind the rank's last block)
         return x if x is not None else self.hidden_1
+
+
+class OutputSample:
+    """--dump-outputs: what the timed path hands back in one job — every attention launch's [1, S, HQ, D] output — as a fixed
+    sample.  Per prefill launch: whole query rows (the first, the last, two seeded ones) and seeded single elements; per decode
+    launch: the whole output of four of the tokens.  Gathered on the launch's own stream right after it (the fused decode step
+    reuses its output buffer); the indices depend only on the arguments, so two builds can be compared file for file."""
+
+    BUDGET = 14 << 20       # float32 elements written in all (56 MB)
+
+    def __init__(self, hp, n_decode, seed=0):
+        import numpy as np
+
+        sizes = [n for _, _, n in hp.blocks] if getattr(hp, "blocks", None) else [c for _, c in hp.chunks]
+        L, row = len(hp.counts), HQ * D
+        self.tokens = sorted({0, n_decode // 3, 2 * n_decode // 3, n_decode - 1}) if n_decode > 0 else []
+        k = min(32768, (self.BUDGET - len(self.tokens) * L * row) // max(1, len(sizes) * L))
+        n_rows = min(4, k // row)
+        rng = np.random.default_rng(seed)
+        self.index = {}
+        for S in sorted(set(sizes)):
+            rows = ([0, S - 1] + [int(r) for r in rng.integers(0, S, size=2)])[:n_rows]
+            idx = np.concatenate([np.arange(r * row, (r + 1) * row) for r in rows] +
+                                 [rng.integers(0, S * row, size=k - len(rows) * row)])
+            self.index[S] = torch.from_numpy(idx).to(hp.device)
+        self.parts = {}
+
+    def add(self, kind, i, li, o):
+        if kind == "prefill":
+            self.parts[(kind, i, li)] = o.reshape(-1).index_select(0, self.index[o.shape[1]])
+        elif i in self.tokens:
+            self.parts[(kind, i, li)] = o.reshape(-1).clone()
+
+    def write(self, out_dir, prefix=""):
+        """<prefix>prefill_attn_out.npy [prefill launches per layer, layers, sampled elements] and <prefix>decode_attn_out.npy
+        [sampled tokens, layers, HQ * D], float32, launch order"""
+        import numpy as np
+
+        torch.cuda.synchronize()
+        os.makedirs(out_dir, exist_ok=True)
+        for kind in ("prefill", "decode"):
+            keys = [k for k in self.parts if k[0] == kind]
+            if not keys:
+                continue
+            items, layers = sorted({k[1] for k in keys}), sorted({k[2] for k in keys})
+            a = torch.stack([torch.stack([self.parts[(kind, i, li)] for li in layers]) for i in items])
+            np.save(os.path.join(out_dir, f"{prefix}{kind}_attn_out.npy"), a.float().cpu().numpy())
 
 
 def sync_all(world):
@@ -991,8 +1048,18 @@ def main():
     ap.add_argument("--cpu-cfg1-layers", type=int, default=1,
                     help="layers of the Llama-2-7B-shape model of the host end-to-end run (cpu_baseline.cfg1_end_to_end); "
                          "32 = the whole model (minutes), 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed job (the full-attention baseline, the CPU baseline, kernel rooflines and "
+                         "their traffic, live parity, INT4, token-row linears, the whole-model run; each still off with its --no-* "
+                         "option); a plain run times the job and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of what the last one's attention launches returned to "
+                         "DIR/*.npy (float32, OutputSample)")
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full and not args.traffic_probe:         # (the traffic child only runs under a --full parent)
+        args.no_full_baseline = args.no_cpu_baseline = args.no_kernel_roofline = args.no_traffic = True
+        args.no_model_level = args.no_parity = args.no_int4 = args.no_token_linear = True
     # stdout carries the ONE JSON line and nothing else: whatever a leg prints on the way (the patch API announces itself
     # like the reference's does: "Enabling DuoAttention evaluation ...") goes to stderr
     # — at the file-descriptor level too: native libraries write to fd 1 directly (gloo reports its rendezvous there)
@@ -1058,15 +1125,17 @@ def main():
     local_counts = [c for lo, hi in lr_blocks for c in counts[lo:hi]]
     n_tok = args.ctx + args.decode_tokens
 
-    def timed(hp, steps, warmup):
+    def timed(hp, steps, warmup, dump=None):
         for _ in range(warmup):
             run_job(hp, pipe, args.decode_tokens, world, device, handoff)
         sync_all(world)
         t0 = time.perf_counter()
         parts, locs = [], []
-        for _ in range(steps):
+        for k in range(steps):
+            hp.dump = dump if k == steps - 1 else None      # (--dump-outputs: the last timed job's launches)
             parts.append(run_job(hp, pipe, args.decode_tokens, world, device, handoff))
             locs.append(run_job.local)
+        hp.dump = None
         sync_all(world)
         t = torch.tensor([time.perf_counter() - t0, sum(p[1] for p in parts), sum(p[2] for p in parts)],
                          device=handoff, dtype=torch.float64)
@@ -1095,8 +1164,12 @@ def main():
         if world > 1:
             raise SystemExit("--block-streams is a one-GPU measurement")
         hp.set_block_streams(args.block_streams)
-    t_job, t_pre, t_dec = timed(hp, args.steps, args.warmup)
+    sample = OutputSample(hp, args.decode_tokens) if args.dump_outputs else None
+    t_job, t_pre, t_dec = timed(hp, args.steps, args.warmup, sample)
     duo_jobs, duo_local = timed.last_jobs, timed.local_jobs
+    if sample is not None:
+        sample.write(args.dump_outputs, f"rank{rank}_" if world > 1 else "")
+        sample = None
 
     # HBM-side traffic per launch is a PMC measurement (rocprofv3 --pmc FETCH_SIZE, its own pass, x2 gfx950
     # correction, MI355X_MICROARCH.md): taken NOW by a child run of this file under rocprofv3 (one prefill pass +

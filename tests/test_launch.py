@@ -83,7 +83,7 @@ def _run_bench(extra_env, *args, timeout=900):
 
 
 SMALL = ["--steps", "1", "--warmup", "0", "--ctx", "8192", "--chunk", "4096", "--layers", "4", "--decode-tokens", "4",
-         "--row-block", "2048", "--no-cpu-baseline", "--no-traffic", "--no-model-level", "--no-int4", "--no-token-linear",
+         "--row-block", "2048", "--full", "--no-cpu-baseline", "--no-traffic", "--no-model-level", "--no-int4", "--no-token-linear",
          "--no-parity"]
 
 

@@ -5,7 +5,7 @@ OLD=$1; N=${2:-3}
 for i in $(seq $N); do
   for lib in "$OLD" duo-attention_amd/lib/libduoattn_hip.so; do
     echo -n "$lib: "
-    DUO_ATTN_HIP_LIB=$PWD/$lib python bench.py --steps 2 --warmup 1 --no-full-baseline --no-cpu-baseline --no-traffic --no-model-level \
+    DUO_ATTN_HIP_LIB=$PWD/$lib python bench.py --steps 2 --warmup 1 --full --no-full-baseline --no-cpu-baseline --no-traffic --no-model-level \
         --no-int4 --no-token-linear --no-parity 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

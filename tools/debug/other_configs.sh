@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 O=$R/gpurun_out/${tag}_other
 mkdir -p $O
 cd $R
-LEAN="--no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity"
+LEAN="--full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity"
 for p in mistral-7b-v0.2@0.5 mistral-7b-v0.2@raw; do
   for c in 4096 32000; do
     python bench.py --pattern $p --ctx 32768 --chunk $c --steps 3 --warmup 1 $LEAN > $O/cfg3_op_${p//[@.]/_}_c$c.json 2>> $O/err.log

@@ -5,7 +5,7 @@
 #  variant legs of this script only document what was run.)
 cd "$(dirname "$0")/../.." || exit 1
 O=gpurun_out/r6_c10; mkdir -p $O
-LEAN="--no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
+LEAN="--full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
 CASE="{'family': 'llama', 'Hkv': 2, 'group': 4, 'inter': 72, 'L': 3, 'heads': [[1.0, 1.0], [1.0, 1.0], [0.0, 0.0]], 'bias': False, 'B': 2, 'sink': 64, 'recent': 8, 'prompt': 127, 'steps': 5, 'evict': True, 'seed': 1715245614}"
 timeout 300 python tests/fuzz_model_decode.py --case "$CASE" 2>&1 | grep -v "amdgpu.ids\|Enabling" | tail -5 | tee $O/case.txt
 timeout 400 python tests/fuzz_model_decode.py --seconds 150 --seed 6004 2>&1 | grep -v "amdgpu.ids\|Enabling" | tail -4 | tee $O/model_decode.txt
@@ -26,7 +26,7 @@ import json; d=json.load(open('$O/job_R${R}_$V.$rep.json')); print('R=$R lib=$V 
 done; done; done
 for V in default dmafirst default dmafirst; do
   if [ $V = default ]; then unset DUO_ATTN_HIP_LIB; else export DUO_ATTN_HIP_LIB=$L/lib_$V.so; fi
-  timeout 600 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx 32768 --chunk 4096 --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity > $O/cfg3_$V.json 2>> $O/job.err
+  timeout 600 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx 32768 --chunk 4096 --steps 3 --warmup 1 --full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity > $O/cfg3_$V.json 2>> $O/job.err
   python -c "
 import json; d=json.load(open('$O/cfg3_$V.json')); print('cfg3 lib=$V', round(d['value']), round(d['prefill_tok_s']), round(d['roofline']['frac'],4), d['speedup_vs_full_attention']['prefill'])" | tee -a $O/jobs.txt
 done

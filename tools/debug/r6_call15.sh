@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../.." || exit 1
 O=gpurun_out/r6_c15; mkdir -p $O
 timeout 900 python -m pytest tests/test_block_streams_gpu.py -x -q -m gpu -p no:cacheprovider > $O/pytest.out 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.out
-LEAN="--no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
+LEAN="--full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
 timeout 600 python bench.py --steps 3 --warmup 1 $LEAN > $O/job_whole.json 2>> $O/job.err
 python -c "
 import json; d=json.load(open('$O/job_whole.json')); print('R=whole', round(d['value']), round(d['prefill_tok_s']), round(d['ms_per_step'],1))" | tee -a $O/jobs.txt

@@ -17,7 +17,7 @@ for cfg in "2048 4 114688 16384" "2048 3 114688 16384" "16384 8 114688 16384" "1
 done | tee $O/wgtime.txt
 echo "== decode at short contexts: one launch vs two, split cap"
 for ctx in 4096 16384 32768; do for ol in 0 1; do
-  echo -n "ctx=$ctx one_launch=$ol  "; DUO_DECODE_ONE_LAUNCH=$ol timeout 300 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx $ctx --chunk 4096 --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d.get('decode_ms_per_token'), d.get('decode_tok_s'))"
+  echo -n "ctx=$ctx one_launch=$ol  "; DUO_DECODE_ONE_LAUNCH=$ol timeout 300 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx $ctx --chunk 4096 --steps 2 --warmup 1 --full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d.get('decode_ms_per_token'), d.get('decode_tok_s'))"
 done; done | tee $O/decode_short.txt
 echo "== graph test file + soak"
 for i in 1 2 3 4 5 6; do timeout 600 python -X faulthandler -m pytest tests/test_auto_graph_gpu.py -x -q -m gpu -p no:cacheprovider > $O/graph_t$i.out 2>&1; echo "run $i rc=$? $(tail -1 $O/graph_t$i.out)"; done | tee $O/graph_runs.txt

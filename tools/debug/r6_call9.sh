@@ -2,7 +2,7 @@
 # round 6, GPU call 9: the prefill kernel's bulk run chained across the pool / chunk boundary — parity, anatomy, same-process-family A/B (debug bit 21 = separate runs)
 cd "$(dirname "$0")/../.." || exit 1
 O=gpurun_out/r6_c9; mkdir -p $O
-LEAN="--no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
+LEAN="--full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
 OLDF=$((1<<21))
 timeout 1800 python -m pytest tests/test_hip_kernels_gpu.py tests/test_full_size_gpu.py tests/test_batched_gpu.py tests/test_golden_and_model_gpu.py tests/test_fuzz_gpu.py tests/test_int4.py tests/test_int4_model_gpu.py tests/test_tuple_path_gpu.py -x -q -m gpu -p no:cacheprovider > $O/pytest.out 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.out
 bash tools/debug/build_variant.sh wgtime -DW64_WGTIME > /dev/null 2>&1
@@ -16,7 +16,7 @@ for rep in 1 2; do for R in whole 4096 2048 1024; do for FL in 0 $OLDF; do
 import json; d=json.load(open('$O/job_R${R}_f$FL.$rep.json')); print('R=$R flags=$FL rep=$rep', round(d['value']), round(d['prefill_tok_s']), round(d['ms_per_step'],1), round(d['roofline']['frac'],4))" | tee -a $O/jobs.txt
 done; done; done
 for FL in 0 $OLDF 0 $OLDF; do
-  DUO_DEBUG_FLAGS=$FL timeout 600 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx 32768 --chunk 4096 --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity > $O/cfg3_f$FL.json 2>> $O/job.err
+  DUO_DEBUG_FLAGS=$FL timeout 600 python bench.py --pattern mistral-7b-v0.2@0.5 --ctx 32768 --chunk 4096 --steps 3 --warmup 1 --full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity > $O/cfg3_f$FL.json 2>> $O/job.err
   python -c "
 import json; d=json.load(open('$O/cfg3_f$FL.json')); print('cfg3 flags=$FL', round(d['value']), round(d['prefill_tok_s']), round(d['roofline']['frac'],4), d['speedup_vs_full_attention']['prefill'])" | tee -a $O/jobs.txt
 done

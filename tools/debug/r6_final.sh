@@ -10,7 +10,7 @@ timeout 2400 python -m pytest tests -x -q -m gpu -p no:cacheprovider > $O/pytest
 cp gpurun_out/parity_report.json $O/parity_report.json 2>/dev/null; cp gpurun_out/model_rel.log $O/model_rel.log 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" 2>&1 | tail -1 | tee $O/smoke.txt
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench rc=$?"
-LEAN="--no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
+LEAN="--full --no-cpu-baseline --no-traffic --no-model-level --no-int4 --no-token-linear --no-parity --no-full-baseline"
 for R_ in whole 4096 2048 1024; do for PL in 1 0; do
   if [ $R_ = whole ]; then DUO_PREFILL_PLANNER=$PL timeout 600 python bench.py --steps 3 --warmup 1 $LEAN > $O/job_R${R_}_planner$PL.json 2>> $O/job.err
   else DUO_PREFILL_PLANNER=$PL DUO_BENCH_FORCE_BLOCKS=1 timeout 600 python bench.py --steps 3 --warmup 1 --row-block $R_ $LEAN > $O/job_R${R_}_planner$PL.json 2>> $O/job.err; fi
@@ -19,7 +19,7 @@ import json; d=json.load(open('$O/job_R${R_}_planner$PL.json')); print('R=$R_ pl
 done; done
 timeout 900 python tools/debug/prefill_launch_map.py --rows 1024 2048 4096 --json $O/map.json > $O/map.out 2> $O/map.err; tail -1 $O/map.out
 # kernel trace of the bench job + the bench line of the same process
-( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_r6 && rocprofv3 --kernel-trace --stats -d /tmp/prof_r6 -o p -- python $R/bench.py --steps 1 --warmup 0 --no-full-baseline --no-cpu-baseline --no-traffic --no-model-level --no-parity > $O/prof_bench.json 2> /tmp/prof_r6.err; python $R/tools/rocpd_summary.py $(find /tmp/prof_r6 -name "*.db" | head -1) --top 14 > $O/kernels.md 2>> $O/job.err )
+( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_r6 && rocprofv3 --kernel-trace --stats -d /tmp/prof_r6 -o p -- python $R/bench.py --steps 1 --warmup 0 --full --no-full-baseline --no-cpu-baseline --no-traffic --no-model-level --no-parity > $O/prof_bench.json 2> /tmp/prof_r6.err; python $R/tools/rocpd_summary.py $(find /tmp/prof_r6 -name "*.db" | head -1) --top 14 > $O/kernels.md 2>> $O/job.err )
 head -12 $O/kernels.md
 # counter passes of the prefill kernel (separate passes, --pmc with --kernel-trace only)
 ( cd /tmp && export TMPDIR=/tmp; i=0
