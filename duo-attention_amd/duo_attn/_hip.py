@@ -18,7 +18,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", "libduoattn_hip.so"))
-ABI_VERSION = 6
+ABI_VERSION = 7
 HEAD_DIM = 128
 
 
@@ -267,6 +267,18 @@ _SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int32, POINTER(Int4Pool), POINTER(Int4Pool), c_float, c_int32,
          c_int32, c_void_p, c_int64, c_void_p],
     ),
+    "duo_lambda_attn_fwd_bf16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+         c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p],
+    ),
+    "duo_lambda_attn_bwd_bf16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+         c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+         c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p],
+    ),
+    "duo_lambda_attn_bwd_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -941,6 +953,65 @@ def silu_mul(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     _check(lib.duo_silu_mul_bf16(g2.data_ptr(), g2.stride(0), u2.data_ptr(), u2.stride(0), y.data_ptr(), y.stride(0),
                                  g2.shape[0], g2.shape[1], _stream_ptr()), "duo_silu_mul_bf16")
     return y.view(gate.shape)
+
+
+def _lambda_shape(q, k, v, sink: int, recent: int, block_mode: int):
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _require_gpu_bf16(t, n)
+        if t.dim() != 4:
+            raise DuoHipError(f"lambda_attn: {n} must be [B, S, heads, D], got {tuple(t.shape)}")
+    B, S, Hq, D = q.shape
+    if k.shape != v.shape or k.shape[0] != B or k.shape[1] != S or D != HEAD_DIM or k.shape[3] != D:
+        raise DuoHipError(f"lambda_attn: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} (head_dim {HEAD_DIM} only)")
+    if sink < 0 or recent < 0 or sink + recent < 1 or block_mode not in (0, 1):
+        raise DuoHipError(f"lambda_attn: sink {sink}, recent {recent}, block_mode {block_mode}")
+    return B, S, Hq, k.shape[2], D
+
+
+def lambda_attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sink: int, recent: int, block_mode: int,
+                    scale: float):
+    """Λ-mask (streaming) attention of the training forward (duo_lambda_attn_fwd_bf16): q [B, S, Hq, D], k / v
+    [B, S, Hkv, D] bf16 views (D contiguous).  block_mode 0: ``sink`` / ``recent`` in tokens; 1: in 128-row blocks.
+    Returns (out [B, S, Hq, D] bf16 contiguous, lse [B, Hq, S] fp32)."""
+    lib = load_library()
+    B, S, Hq, Hkv, D = _lambda_shape(q, k, v, sink, recent, block_mode)
+    out = torch.empty(B, S, Hq, D, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, S, dtype=torch.float32, device=q.device)
+    _check(lib.duo_lambda_attn_fwd_bf16(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+                                        k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
+                                        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
+                                        out.data_ptr(), lse.data_ptr(), B, S, Hq, Hkv, D, int(sink), int(recent),
+                                        int(block_mode), float(scale), _stream_ptr()), "duo_lambda_attn_fwd_bf16")
+    return out, lse
+
+
+def lambda_attn_bwd(q, k, v, out, lse, dout, sink: int, recent: int, block_mode: int, scale: float):
+    """Backward of ``lambda_attn_fwd`` (duo_lambda_attn_bwd_bf16; deterministic).  ``out`` / ``lse``: what the forward
+    returned; ``dout`` [B, S, Hq, D] at any strides with D contiguous.  Returns (dq, dk, dv), bf16 contiguous."""
+    lib = load_library()
+    B, S, Hq, Hkv, D = _lambda_shape(q, k, v, sink, recent, block_mode)
+    _require_gpu_bf16(out, "out")
+    if dout.stride(-1) != 1 or any(s % 8 for s in dout.stride()[:3]) or dout.data_ptr() % 16:
+        dout = dout.contiguous()
+    _require_gpu_bf16(dout, "dout")
+    out = out.contiguous()
+    lse = lse.contiguous()
+    if dout.shape != q.shape or out.shape != q.shape or lse.shape != (B, Hq, S) or lse.dtype != torch.float32:
+        raise DuoHipError(f"lambda_attn_bwd: out {tuple(out.shape)}, dout {tuple(dout.shape)}, lse {tuple(lse.shape)}")
+    nbytes = lib.duo_lambda_attn_bwd_workspace_bytes(B, S, Hq, Hkv, int(sink), int(recent), int(block_mode))
+    _check(min(int(nbytes), 0), "duo_lambda_attn_bwd_workspace_bytes")
+    ws = torch.empty((int(nbytes) + 15) // 16 * 4, dtype=torch.float32, device=q.device)
+    dq = torch.empty(B, S, Hq, D, dtype=torch.bfloat16, device=q.device)
+    dk = torch.empty(B, S, Hkv, D, dtype=torch.bfloat16, device=q.device)
+    dv = torch.empty_like(dk)
+    _check(lib.duo_lambda_attn_bwd_bf16(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+                                        k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
+                                        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
+                                        out.data_ptr(), dout.data_ptr(), dout.stride(0), dout.stride(1), dout.stride(2),
+                                        lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+                                        ws.numel() * 4, B, S, Hq, Hkv, D, int(sink), int(recent), int(block_mode),
+                                        float(scale), _stream_ptr()), "duo_lambda_attn_bwd_bf16")
+    return dq, dk, dv
 
 
 def token_linear_fits(n_rows: int, n_in: int) -> bool:

@@ -129,6 +129,14 @@ class HipBackend:
     def decode_layer_batched_dev(self, *args, **kw) -> None:
         return self._hip.decode_layer_batched_dev(*args, **kw)
 
+    # -- retrieval-head training: the streaming branch's Λ-mask attention (reference streaming_attn.py:14-43,70-108) and its
+    #    backward.  q [B, S, Hq, D], k / v [B, S, Hkv, D]; block_mode 0: sink / recent in tokens, 1: in 128-row blocks
+    def lambda_attn_fwd(self, q, k, v, sink: int, recent: int, block_mode: int, scale: float):
+        return self._hip.lambda_attn_fwd(q, k, v, sink, recent, block_mode, scale)
+
+    def lambda_attn_bwd(self, q, k, v, out, lse, dout, sink: int, recent: int, block_mode: int, scale: float):
+        return self._hip.lambda_attn_bwd(q, k, v, out, lse, dout, sink, recent, block_mode, scale)
+
 
 _backend = None
 

@@ -811,10 +811,11 @@ def enable_duo_attention_static_kv_cache_eval(model, full_attention_heads):
 
 def enable_duo_attention_training(model, sink_size, recent_size, max_length, initial_value=1.0,
                                   enable_ulysses_attention=False, streaming_attn_implementation="blocksparse"):
-    raise NotImplementedError(
-        "Retrieval-head identification (training, reference llama.py:437-501) is outside the MI355X "
-        "hot-path scope; use the shipped attn_patterns."
-    )
+    """Retrieval-head training patch (reference llama.py:437-501): duo_attn/patch/training.py"""
+    from .training import enable_duo_attention_training as enable
+
+    enable(model, sink_size, recent_size, max_length, initial_value=initial_value,
+           enable_ulysses_attention=enable_ulysses_attention, streaming_attn_implementation=streaming_attn_implementation)
 
 
 def _attn_modules(model):

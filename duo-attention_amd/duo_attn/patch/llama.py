@@ -17,10 +17,12 @@ from .static_kv_cache import (  # noqa: F401
     DuoAttentionStaticKVCache,
     enable_duo_attention_static_kv_cache_for_llama,
 )
+from .training import duo_attention_forward_two_way as llama_duo_attention_forward_two_way  # noqa: F401
 from .tuple_kv_cache import enable_tuple_kv_cache_for_llama  # noqa: F401
 
 __all__ = [
     "llama_duo_attention_forward_one_way_reordered",
+    "llama_duo_attention_forward_two_way",
     "llama_duo_attention_forward_one_way_reordered_static",
     "enable_llama_duo_attention_eval",
     "enable_llama_duo_attention_static_kv_cache_eval",

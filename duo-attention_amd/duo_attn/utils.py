@@ -260,6 +260,14 @@ def sparsify_attention_heads(full_attention_heads, threshold=None, sparsity=None
     return full_attention_heads, 1 - np.mean(full_attention_heads)
 
 
+def full_attention_heads_to_list(full_attention_heads):
+    """reference utils.py:302-309: every layer's gate tensor replaced, IN the given list, by a list of floats (detached,
+    fp32, on the host); returns the same list"""
+    for idx in range(len(full_attention_heads)):
+        full_attention_heads[idx] = full_attention_heads[idx].detach().float().cpu().tolist()
+    return full_attention_heads
+
+
 def save_full_attention_heads(full_attention_heads, output_filename):
     heads = full_attention_heads
     if hasattr(heads, "detach"):           # torch tensor (or a list of them, below) -> numpy, no copy keyword games

@@ -53,6 +53,8 @@
  * ABI version 6 (round 6, two additions, no signature changed): + duo_debug_prefill_last_plan, duo_debug_prefill_plan; the prefill entry points choose
  *   key-range splits for BOTH head classes (up to 16 pieces) by replaying the launch on the chip's 256 CUs, and
  *   duo_attn_prefill_workspace_bytes() doubled (2048 partials).  Results of a launch may be split — summed — differently than by a v5 build; outputs stay inside the same bar.
+ * ABI version 7 (additions only, no signature changed): + duo_lambda_attn_fwd_bf16, duo_lambda_attn_bwd_bf16,
+ *   duo_lambda_attn_bwd_workspace_bytes — the Λ-mask (streaming) attention of retrieval-head training, with its backward.
  *
  * Attention semantics (flash-attn 2.6.3 flash_attn_func, causal=True,
  * bottom-right aligned): a query at row i of the S new rows sees every key of
@@ -69,7 +71,7 @@
 extern "C" {
 #endif
 
-#define DUO_ABI_VERSION 6
+#define DUO_ABI_VERSION 7
 
 /* argument errors (negative so they never collide with hipError_t) */
 #define DUO_EINVAL   (-1)  /* bad pointer / size / stride                     */
@@ -561,6 +563,40 @@ int duo_rope_hf_inplace_bf16(void *q, int64_t q_token_stride, int64_t q_head_str
                              const void *cos_rows, const void *sin_rows, int64_t cos_sin_token_stride, int32_t head_dim,
                              void *stream);
 int duo_rmsnorm_hf_bf16(const void *x, const void *w, void *y, int64_t n_rows, int32_t hidden, float eps, void *stream);
+
+/* ---- retrieval-head training: Λ-mask ("streaming") attention, forward and backward --------------------------------------
+ * The streaming branch of the two-way training forward (reference llama.py:113-118): streaming_attn_sdpa with
+ * generate_streaming_mask (streaming_attn.py:14-43, block_mode = 0) or streaming_attn_blocksparse_flash_attn
+ * (streaming_attn.py:70-108, block_mode = 1), and the autograd backward of either.  Query row i (0 = first token) sees key
+ * j iff j <= i and
+ *   block_mode 0 (token):  j < sink or j > i - recent                       (sink, recent in tokens)
+ *   block_mode 1 (block):  j / 128 < sink or i / 128 - j / 128 < recent     (sink, recent = sink / local 128-row block counts,
+ *                                                                            the local blocks include the diagonal one)
+ * a key in both ranges counts once; sink + recent >= 1.  q [B, S, Hq, 128], k / v [B, S, Hkv, 128] at element strides
+ * (batch, token, head; multiples of 8, 16-byte aligned bases); GQA q head h uses kv head h / (Hq / Hkv).  fp32 scores, softmax
+ * and accumulation; P rounded to bf16 before P.V.
+ * duo_lambda_attn_fwd_bf16: out [B, S, Hq, 128] bf16 contiguous, lse [B, Hq, S] fp32 (natural log of the row's sum of
+ * exp(score * scale)).
+ * duo_lambda_attn_bwd_bf16: FA2 convention — P recomputed from q, k and lse; delta = rowsum(dout o out); dS = P o (dP - delta)
+ * in fp32, rounded to bf16 before the dq / dk products, P rounded to bf16 before the dv product.  out = the forward's
+ * output (contiguous); dout at its own strides; dq [B, S, Hq, 128], dk / dv [B, S, Hkv, 128] bf16 contiguous, written whole.
+ * Deterministic: no float atomics (the sink keys' query range is split into fp32 partials summed in a fixed order), so
+ * a rerun is bit-identical.  workspace >= duo_lambda_attn_bwd_workspace_bytes(...) bytes, 16-byte aligned (that call
+ * returns a negative DUO_E* code for an argument error). */
+int duo_lambda_attn_fwd_bf16(const void *q, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                             const void *k, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_head_stride,
+                             const void *v, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_head_stride,
+                             void *out, float *lse, int32_t B, int32_t S, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                             int32_t sink, int32_t recent, int32_t block_mode, float scale, void *stream);
+int duo_lambda_attn_bwd_bf16(const void *q, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                             const void *k, int64_t k_batch_stride, int64_t k_token_stride, int64_t k_head_stride,
+                             const void *v, int64_t v_batch_stride, int64_t v_token_stride, int64_t v_head_stride,
+                             const void *out, const void *dout, int64_t do_batch_stride, int64_t do_token_stride,
+                             int64_t do_head_stride, const float *lse, void *dq, void *dk, void *dv, void *workspace,
+                             int64_t workspace_bytes, int32_t B, int32_t S, int32_t Hq, int32_t Hkv, int32_t head_dim,
+                             int32_t sink, int32_t recent, int32_t block_mode, float scale, void *stream);
+int64_t duo_lambda_attn_bwd_workspace_bytes(int32_t B, int32_t S, int32_t Hq, int32_t Hkv, int32_t sink, int32_t recent,
+                                            int32_t block_mode);
 
 #ifdef __cplusplus
 }
