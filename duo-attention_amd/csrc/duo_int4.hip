@@ -18,7 +18,6 @@
 // strides are arguments, so the reference's token-major pools work too.
 #include <hip/hip_fp16.h>
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include "duo_common.h"
 
@@ -460,9 +459,6 @@ __global__ __launch_bounds__(256) void duo_int4_decode_split_kernel(const Int4De
 // 16+4g+e-4: no cross-lane traffic for P.
 // Softmax keeps a per-q-head reference maximum that is only raised when some score exceeds it by 2^8
 // (wave vote), so the steady state has no cross-lane reduction and no accumulator rescale.
-#ifndef DUO_I4_PROBE
-#define DUO_I4_PROBE 0      // ablation builds only (wrong results by design): bit 0 no exp, bit 1 no K dequantisation, bit 2 no V, bit 3 no LDS transpose
-#endif
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 
@@ -505,14 +501,28 @@ __device__ __forceinline__ bool scales_in_fma_range(uint32_t a, uint32_t b, uint
     return ((x | y) & 0xC000C000u) == 0u;
 }
 
+// Nibble masks 0x000f000f / 0x00f000f0 and half2(1024, 1024), opaque to the optimiser (masks in SGPRs, the exponent word in
+// a VGPR) so that (w & mask) | magic is ONE v_and_or_b32: as literals the pair needs two instructions (one literal per VOP3
+// on gfx9)
+struct I4Masks {
+    uint32_t m0, m4, magic;
+};
+__device__ __forceinline__ I4Masks i4_masks() {
+    I4Masks M;
+    asm volatile("s_mov_b32 %0, 0x000f000f" : "=s"(M.m0));
+    asm volatile("s_mov_b32 %0, 0x00f000f0" : "=s"(M.m4));
+    asm volatile("v_mov_b32 %0, 0x64006400" : "=v"(M.magic));
+    return M;
+}
+
 // one packed dword (8 nibbles) -> 4 x half2 of reference-exact dequantised values, element order
-// [1,5 | 0,4 | 3,7 | 2,6] of the dword's 8 dims.  m0 / m4: nibble masks 0x000f000f / 0x00f000f0 (SGPRs),
-// magic: half2(1024, 1024) (VGPR) — see the note at their definition.
+// [1,5 | 0,4 | 3,7 | 2,6] of the dword's 8 dims.
 // FUSED: the one-rounding form fma(n, s, z) (see dequant8_pk): (1024 + n) - 1024 = n and (1024 + 16 n) - 1024 = 16 n
 // are exact, then one fma against s (or s / 16, exact for voted tiles) — the same 13 / 19 instructions per 8 values.
 template <bool FAST, bool FUSED>
-__device__ __forceinline__ u32x4 dq8(uint32_t w, const RowConst &R, uint32_t m0, uint32_t m4, uint32_t magic) {
+__device__ __forceinline__ u32x4 dq8(uint32_t w, const RowConst &R, const I4Masks &K) {
 #pragma clang fp contract(off)
+    const uint32_t m0 = K.m0, m4 = K.m4, magic = K.magic;
     u32x4 o;
     const h2_t bias = h2_splat(1024.f);
     if constexpr (FAST) {
@@ -554,9 +564,6 @@ __device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
 }
 __device__ __forceinline__ f16x8_t as_f16x8(const u32x4 &w) { return *reinterpret_cast<const f16x8_t *>(&w); }
 
-#define DUO_I4_TR_READ(dst, addr, off) \
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-
 struct I4Tile {
     u32x4 kw[2], vw[2];
     uint32_t ks[2], vs[2];
@@ -564,42 +571,139 @@ struct I4Tile {
 
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
-// MINW: waves per SIMD the register budget is cut for; MODE: 0 = every tile in the always-exact shifted form, 1 = voted
-// (tiles whose scales allow it take the masked form); FUSED: fma(n, s, z) instead of hadd(hmul(n, s), z) (see dq8).
-template <int MINW, int MODE, bool FUSED>
-__global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const Int4DecodeParams P) {
+// ---- what the two matrix-core kernels below (dequantising and folded) have in common -------------------------------
+// What a workgroup and each of its four waves work on: block -> head class, kv head, split; the split's balanced share of
+// the 64-key units; a quarter of it (whole 32-key tiles) per wave; the uniform (SGPR) row bases of the kv head.
+struct I4Work {
+    Int4SegDev C;
+    int kvh, split, splits, qh0;
+    int w0, w1;                             // this wave's key range
+    const uint8_t *kq, *vq, *ksz, *vsz;     // row 0 of the kv head: 64 B of nibbles / 4 B of (scale, zero) per row
+};
+__device__ __forceinline__ I4Work i4_work(const Int4DecodeParams &P, int wave) {
+    I4Work W;
+    int b = blockIdx.x;
+    const int ci = b < P.nblk_full ? 0 : 1;
+    if (ci) b -= P.nblk_full;
+    W.C = i4_select(P.cls[0], P.cls[1], ci != 0);
+    W.splits = ci ? P.splits[1] : P.splits[0];
+    W.kvh = b / W.splits;
+    W.split = b - W.kvh * W.splits;
+    W.qh0 = W.C.q_head_offset + W.kvh * P.group;
+
+    const int L = W.C.len;
+    const int units = (L + 63) >> 6;
+    const int uq = units / W.splits, ur = units - uq * W.splits;
+    const int u0 = W.split * uq + min(W.split, ur);
+    const int un = uq + (W.split < ur ? 1 : 0);
+    const int c0 = u0 << 6;
+    const int c1 = min((u0 + un) << 6, L);
+    const int per_wave = (((c1 - c0 + 3) >> 2) + 31) & ~31;   // quarter of the chunk, whole 32-key tiles
+    W.w0 = __builtin_amdgcn_readfirstlane(c0 + wave * per_wave);
+    W.w1 = __builtin_amdgcn_readfirstlane(min(W.w0 + per_wave, c1));
+
+    const int64_t head_row = (int64_t)W.kvh * W.C.hs + (int64_t)blockIdx.z * W.C.bs;     // (grid.z = batch row)
+    W.kq = W.C.kq + head_row * 64;
+    W.vq = W.C.vq + head_row * 64;
+    W.ksz = reinterpret_cast<const uint8_t *>(W.C.ksz) + head_row * 4;
+    W.vsz = reinterpret_cast<const uint8_t *>(W.C.vsz) + head_row * 4;
+    return W;
+}
+
+// Addresses in a wave's 8 KiB V^ tile, [32 keys][16 chunks of 16 B], chunk c of key k stored at slot c ^ (k & 15).
+// wa[j]: where lane (r, g) writes chunk 4g + j of key r (+ 4096: key 16 + r).
+// ra: transpose read — lane i of a 16-lane group supplies the 8-byte piece (row i>>2, cols 4(i&3)..+3) of a 4 x 16 block
+// and receives column i;  rows 4g..4g+3 (and +16), dim block nb -> address ^ (nb << 5)
+__device__ __forceinline__ uint32_t i4_lds_wa(uint32_t lbase, int r, int g, int j) { return lbase + r * 256 + (((4 * g + j) ^ r) << 4); }
+__device__ __forceinline__ uint32_t i4_lds_ra(uint32_t lbase, int r, int g) {
+    const int kr = 4 * g + (r >> 2);
+    return lbase + kr * 256 + ((((r >> 1) & 1) ^ (kr & 15)) << 4) + 8 * (r & 1);
+}
+
+// a uniform address as an SGPR pair in the global address space: the loads then take the sgpr-base + vgpr32-offset form
+typedef __attribute__((address_space(1))) const uint8_t gbyte_t;
+typedef __attribute__((address_space(1))) const u32x4 gu32x4_t;
+typedef __attribute__((address_space(1))) const uint32_t gu32_t;
+__device__ __forceinline__ gbyte_t *ubase(const uint8_t *p) {
+    const uint64_t a = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return (gbyte_t *)(((uint64_t)hi << 32) | lo);
+}
+
+// O += P . V^ from the wave's LDS tile: transpose reads two dim blocks at a time, one batch ahead of the MFMAs, with counted
+// lgkmcnt waits.  (Macros, not loops over functions: ds_read_b64_tr_b16 takes its offset as an immediate.)
+__device__ __forceinline__ void i4_pv(const f16x8_t &pA, uint32_t ra, f32x4 (&O)[8]) {
+    u32x2 va[4], vb[4];
+    __builtin_amdgcn_sched_barrier(0);
+#define DUO_I4_TR_READ(dst, addr, off) \
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
+#define DUO_I4_TR_BATCH(buf, nb0)                                                   \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                              \
+        uint32_t a_ = ra ^ (uint32_t)(((nb0) + i_) << 5);                           \
+        DUO_I4_TR_READ(buf[2 * i_], a_, 0);                                         \
+        DUO_I4_TR_READ(buf[2 * i_ + 1], a_, 4096);                                  \
+    }
+#define DUO_I4_PV(buf, nb0)                                                                              \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                   \
+        const u32x4 w_ = {buf[2 * i_].x, buf[2 * i_].y, buf[2 * i_ + 1].x, buf[2 * i_ + 1].y};           \
+        O[(nb0) + i_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pA, as_f16x8(w_), O[(nb0) + i_], 0, 0, 0); \
+    }
+#define DUO_I4_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+    DUO_I4_TR_BATCH(va, 0);
+    DUO_I4_TR_BATCH(vb, 2);
+    DUO_I4_WAIT(4);
+    DUO_I4_PV(va, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    DUO_I4_TR_BATCH(va, 4);
+    DUO_I4_WAIT(4);
+    DUO_I4_PV(vb, 2);
+    __builtin_amdgcn_sched_barrier(0);
+    DUO_I4_TR_BATCH(vb, 6);
+    DUO_I4_WAIT(4);
+    DUO_I4_PV(va, 4);
+    DUO_I4_WAIT(0);
+    DUO_I4_PV(vb, 6);
+#undef DUO_I4_TR_READ
+#undef DUO_I4_TR_BATCH
+#undef DUO_I4_PV
+#undef DUO_I4_WAIT
+}
+
+// Some score exceeds the reference maximum by more than 2^8 (the caller has voted): raise the reference to the true running
+// maximum of every q column and rescale the accumulators.  O rows are q heads 4g + e: their factors are fetched from the lanes
+// that own those columns; L (optional) holds sums laid out as O's rows.  Returns this lane's own factor (q column r).
+// (L is scaled inside the row loop, and the fold kernel scales its per-column sums from the return value, because that is the
+// order the kernels had it in: handing the row factors back to the caller instead costs the mfma kernels an s_waitcnt.)
+__device__ __forceinline__ float i4_raise_ref(float mx, float &m_ref, f32x4 (&O)[8], int g, f32x4 *L = nullptr) {
+    float tm = fmaxf(mx, __shfl_xor(mx, 16));
+    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    const float m_new = fmaxf(m_ref, tm);
+    const float alpha = fast_exp2(m_ref - m_new);
+    m_ref = m_new;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float a = __shfl(alpha, 4 * g + e);
+        if (L) (*L)[e] *= a;
+#pragma unroll
+        for (int nb = 0; nb < 8; ++nb) O[nb][e] *= a;
+    }
+    return alpha;
+}
+
+// FUSED: fma(n, s, z) instead of hadd(hmul(n, s), z) (see dq8).  Tiles whose scales allow it (wave vote) take the masked
+// exact-fma form, the others the always-exact shifted form.
+template <bool FUSED>
+__global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4DecodeParams P) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15;    // key row inside a 16-key half / q column / dim column
     const int g = lane >> 4;    // 16-byte quarter of the packed row / k-slot group
 
-    int b = blockIdx.x;
-    const int ci = b < P.nblk_full ? 0 : 1;
-    if (ci) b -= P.nblk_full;
-    const Int4SegDev C = i4_select(P.cls[0], P.cls[1], ci != 0);
-    const int splits = ci ? P.splits[1] : P.splits[0];
-    const int kvh = b / splits;
-    const int split = b - kvh * splits;
-    const int qh0 = C.q_head_offset + kvh * P.group;
+    const I4Work W = i4_work(P, wave);
+    const int w0 = W.w0, w1 = W.w1, qh0 = W.qh0, splits = W.splits, split = W.split;
 
-    const int L = C.len;
-    const int units = (L + 63) >> 6;
-    const int uq = units / splits, ur = units - uq * splits;
-    const int u0 = split * uq + min(split, ur);
-    const int un = uq + (split < ur ? 1 : 0);
-    const int c0 = u0 << 6;
-    const int c1 = min((u0 + un) << 6, L);
-    const int per_wave = (((c1 - c0 + 3) >> 2) + 31) & ~31;   // quarter of the chunk, whole 32-key tiles
-    const int w0 = __builtin_amdgcn_readfirstlane(c0 + wave * per_wave);
-    const int w1 = __builtin_amdgcn_readfirstlane(min(w0 + per_wave, c1));
-
-    // uniform (SGPR) row bases of this kv head + per-lane 32-bit byte offsets inside a 32-key tile
-    const int64_t head_row = (int64_t)kvh * C.hs + (int64_t)blockIdx.z * C.bs;     // (grid.z = batch row)
-    const uint8_t *kq = C.kq + head_row * 64;
-    const uint8_t *vq = C.vq + head_row * 64;
-    const uint8_t *ksz = reinterpret_cast<const uint8_t *>(C.ksz) + head_row * 4;
-    const uint8_t *vsz = reinterpret_cast<const uint8_t *>(C.vsz) + head_row * 4;
-    const int64_t ts = C.ts;
+    // per-lane 32-bit byte offsets inside a 32-key tile
+    const int64_t ts = W.C.ts;
     const uint32_t row_b = (uint32_t)ts * 64u, sz_b = (uint32_t)ts * 4u;   // bytes per token step
     const uint32_t qoff0 = (uint32_t)r * row_b + g * 16, qoff1 = qoff0 + 16u * row_b;
     const uint32_t soff0 = (uint32_t)r * sz_b, soff1 = soff0 + 16u * sz_b;
@@ -623,34 +727,13 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
     const f16x8_t ones = as_f16x8(ones_w);
 
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * 8192];
-    // four-wave form: the Q^T fragments (16 registers) live in LDS and are re-read per tile — they are only needed while
-    // S is formed, and 128 registers do not hold them through the V half of the tile body as well
-    // (one copy per workgroup: the four waves hold the same fragments — same kv head, same q heads, same lane layout)
-    __shared__ __attribute__((aligned(16))) uint8_t lds_q[MINW == 4 ? 4096 : 16];
-    const uint32_t qaddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)lds_q + lane * 16;
-    if constexpr (MINW == 4) {
-        if (wave == 0) {
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) *(lds_u32x4 *)(uintptr_t)(qaddr + kb * 1024) = *reinterpret_cast<const u32x4 *>(&qB[kb]);
-        }
-        __syncthreads();
-    }
-    // V^ tile of this wave: [32 keys][16 chunks of 16 B], chunk c of key k stored at slot c ^ (k & 15)
     const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)lds + wave * 8192;
     uint32_t wa[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wa[j] = lbase + r * 256 + (((4 * g + j) ^ r) << 4);
-    // transpose read: lane i of a 16-lane group supplies the 8-byte piece (row i>>2, cols 4(i&3)..+3) of a
-    // 4 x 16 block and receives column i;  rows 4g..4g+3 (and +16), dim block nb -> address ^ (nb << 5)
-    const int kr = 4 * g + (r >> 2);
-    const uint32_t ra = lbase + kr * 256 + ((((r >> 1) & 1) ^ (kr & 15)) << 4) + 8 * (r & 1);
+    for (int j = 0; j < 4; ++j) wa[j] = i4_lds_wa(lbase, r, g, j);
+    const uint32_t ra = i4_lds_ra(lbase, r, g);
 
-    // opaque to the optimiser (masks in SGPRs, the exponent word in a VGPR) so that (w & mask) | magic is
-    // ONE v_and_or_b32: as literals the pair needs two instructions (one literal per VOP3 on gfx9)
-    uint32_t m0, m4, magic;
-    asm volatile("s_mov_b32 %0, 0x000f000f" : "=s"(m0));
-    asm volatile("s_mov_b32 %0, 0x00f000f0" : "=s"(m4));
-    asm volatile("v_mov_b32 %0, 0x64006400" : "=v"(magic));
+    const I4Masks K = i4_masks();
 
     f32x4 O[8], Lacc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -662,33 +745,9 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
     // re-materialises each 32-bit offset in the basic block of the loads so that they select the
     // sgpr-base + vgpr32-offset addressing form; in place, so no temporary register is involved.)
     uint32_t qo0 = qoff0, qo1 = qoff1, so0 = soff0, so1 = soff1;
-    typedef __attribute__((address_space(1))) const uint8_t gbyte_t;
-    typedef __attribute__((address_space(1))) const u32x4 gu32x4_t;
-    typedef __attribute__((address_space(1))) const uint32_t gu32_t;
-    auto ubase = [&](const uint8_t *p) __attribute__((always_inline)) {
-        const uint64_t a = (uint64_t)p;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return (gbyte_t *)(((uint64_t)hi << 32) | lo);
-    };
-    auto load_k_at = [&](int t, I4Tile &T, uint32_t &q0, uint32_t &q1, uint32_t &s0, uint32_t &s1) __attribute__((always_inline)) {
-        gbyte_t *kq_t = ubase(kq + (int64_t)t * ts * 64), *ks_t = ubase(ksz + (int64_t)t * ts * 4);
-        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(s0), "+v"(s1));
-        T.kw[0] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + q0));
-        T.kw[1] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + q1));
-        T.ks[0] = __builtin_nontemporal_load(reinterpret_cast<gu32_t *>(ks_t + s0));
-        T.ks[1] = __builtin_nontemporal_load(reinterpret_cast<gu32_t *>(ks_t + s1));
-    };
-    auto load_v_at = [&](int t, I4Tile &T, uint32_t &q0, uint32_t &q1, uint32_t &s0, uint32_t &s1) __attribute__((always_inline)) {
-        gbyte_t *vq_t = ubase(vq + (int64_t)t * ts * 64), *vs_t = ubase(vsz + (int64_t)t * ts * 4);
-        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(s0), "+v"(s1));
-        T.vw[0] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(vq_t + q0));
-        T.vw[1] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(vq_t + q1));
-        T.vs[0] = __builtin_nontemporal_load(reinterpret_cast<gu32_t *>(vs_t + s0));
-        T.vs[1] = __builtin_nontemporal_load(reinterpret_cast<gu32_t *>(vs_t + s1));
-    };
     auto load_at = [&](int t, I4Tile &T, uint32_t &q0, uint32_t &q1, uint32_t &s0, uint32_t &s1) __attribute__((always_inline)) {
-        gbyte_t *kq_t = ubase(kq + (int64_t)t * ts * 64), *vq_t = ubase(vq + (int64_t)t * ts * 64);
-        gbyte_t *ks_t = ubase(ksz + (int64_t)t * ts * 4), *vs_t = ubase(vsz + (int64_t)t * ts * 4);
+        gbyte_t *kq_t = ubase(W.kq + (int64_t)t * ts * 64), *vq_t = ubase(W.vq + (int64_t)t * ts * 64);
+        gbyte_t *ks_t = ubase(W.ksz + (int64_t)t * ts * 4), *vs_t = ubase(W.vsz + (int64_t)t * ts * 4);
         asm volatile("" : "+v"(q0), "+v"(q1), "+v"(s0), "+v"(s1));
         T.kw[0] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + q0));
         T.kw[1] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + q1));
@@ -708,39 +767,11 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
         uint32_t s0 = (uint32_t)r0 * sz_b, s1 = (uint32_t)r1 * sz_b;
         load_at(t, T, q0, q1, s0, s1);
     };
-    // SPLIT form (four waves per SIMD): the K half and the V half of a tile are fetched separately into ONE tile buffer —
-    // tile t + 32 if it lies in the range (rows past the range re-read its last row), else the range's last tile again
-    // (never consumed), so the number of loads in flight is the same on every path
-    auto load_half = [&](int tn, I4Tile &T, auto k_tag) __attribute__((always_inline)) {
-        constexpr bool KH = decltype(k_tag)::value;
-        const int t = tn < w1 ? tn : w0 + (((w1 - 1 - w0) >> 5) << 5);
-        if (t + 32 <= w1) {
-            if constexpr (KH) load_k_at(t, T, qo0, qo1, so0, so1);
-            else load_v_at(t, T, qo0, qo1, so0, so1);
-        } else {
-            const int last = w1 - 1 - t;
-            const int r0 = min(r, last), r1 = min(16 + r, last);
-            uint32_t q0 = (uint32_t)r0 * row_b + g * 16, q1 = (uint32_t)r1 * row_b + g * 16;
-            uint32_t s0 = (uint32_t)r0 * sz_b, s1 = (uint32_t)r1 * sz_b;
-            if constexpr (KH) load_k_at(t, T, q0, q1, s0, s1);
-            else load_v_at(t, T, q0, q1, s0, s1);
-        }
-    };
 
     // K half of the tile body: S^T = K^ . Q^T.  FAST: the exact-fma dequantisation (every K row scale of the tile in range —
     // the caller has voted); otherwise subtract-multiply-add.
     auto process_k = [&](const I4Tile &T, f32x4 (&S)[2], auto fast_tag) __attribute__((always_inline)) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        f16x8_t qk[4];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            if constexpr (MINW == 4) {      // (volatile: re-read per tile, never hoisted back into registers)
-                const u32x4 w = *(volatile lds_u32x4 *)(uintptr_t)(qaddr + kb * 1024);
-                qk[kb] = as_f16x8(w);
-            } else {
-                qk[kb] = qB[kb];
-            }
-        }
         // ---- S^T = K^ . Q^T ------------------------------------------------------------------
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -748,18 +779,12 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
             const RowConst R = row_const(T.ks[h], FAST);
             const uint32_t kw[4] = {T.kw[h].x, T.kw[h].y, T.kw[h].z, T.kw[h].w};
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) {
-#if DUO_I4_PROBE & 2     // ablation build (tools/debug/int4_ablation.sh): K words to the MFMA without dequantisation
-                const u32x4 raw = {kw[kb] & 0x3bff3bffu, (kw[kb] >> 1) & 0x3bff3bffu, R.s[0] != R.z[1] ? kw[kb] & 0x33ff33ffu : 0u, 0u};
-                S[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(raw), qk[kb], S[h], 0, 0, 0);
-#else
-                S[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(dq8<FAST, FUSED>(kw[kb], R, m0, m4, magic)), qk[kb],
-                                                              S[h], 0, 0, 0);
-#endif
-            }
+            for (int kb = 0; kb < 4; ++kb)
+                S[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(dq8<FAST, FUSED>(kw[kb], R, K)), qB[kb], S[h], 0, 0, 0);
         }
     };
-    // V half: V^ -> LDS, softmax of S against the reference maximum, O += P . V^.  TAIL: partial tile, keys past the range masked.
+    // V half: V^ -> LDS, then (softmax_pv) softmax of S against the reference maximum and O += P . V^.  TAIL: partial tile,
+    // keys past the range masked.
     auto v_to_lds = [&](const I4Tile &T, auto fast_tag) __attribute__((always_inline)) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // ---- V^ -> LDS (issued early: the writes drain while the softmax runs) -----------------
@@ -768,31 +793,18 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
             const RowConst R = row_const(T.vs[h], FAST);
             const uint32_t vw[4] = {T.vw[h].x, T.vw[h].y, T.vw[h].z, T.vw[h].w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#if DUO_I4_PROBE & 8
-                if (R.s[0] != R.s[0]) m_ref += 1.f;     // (keeps the scale loads alive)
-#elif DUO_I4_PROBE & 4     // ablation build: V words to LDS without dequantisation
-                *(lds_u32x4 *)(uintptr_t)(wa[j] + h * 4096) = u32x4{vw[j] & 0x3bff3bffu, (vw[j] >> 1) & 0x3bff3bffu, R.s[0] != R.z[1] ? vw[j] & 0x33ff33ffu : 0u, 0u};
-#else
-                *(lds_u32x4 *)(uintptr_t)(wa[j] + h * 4096) = dq8<FAST, FUSED>(vw[j], R, m0, m4, magic);
-#endif
-            }
+            for (int j = 0; j < 4; ++j) *(lds_u32x4 *)(uintptr_t)(wa[j] + h * 4096) = dq8<FAST, FUSED>(vw[j], R, K);
         }
     };
-    // tail: std::true_type / std::false_type (a compile-time choice), or a bool decided per tile (four-wave form: ONE copy of
-    // this body in the loop — with one copy per case the accumulators are shuffled between registers where the cases meet)
-    auto softmax_pv = [&](const I4Tile &T, int t, const f32x4 (&S)[2], auto tail) __attribute__((always_inline)) {
-        (void)T;
-        bool is_tail;
-        if constexpr (std::is_same<decltype(tail), bool>::value) is_tail = tail;
-        else is_tail = decltype(tail)::value;
+    auto softmax_pv = [&](int t, const f32x4 (&S)[2], auto tail_tag) __attribute__((always_inline)) {
+        constexpr bool TAIL = decltype(tail_tag)::value;
         // ---- softmax against the reference maximum ---------------------------------------------
         float sv[8];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int e = 0; e < 4; ++e) sv[4 * h + e] = S[h][e];
-        if (is_tail) {   // keys past the range score -inf
+        if constexpr (TAIL) {   // keys past the range score -inf
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -801,31 +813,12 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
         }
         const float mx = c_ * fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])),
                                     fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
-        if (__any(mx > m_ref + 8.f)) {
-            // raise the reference: true running maximum of every q column, accumulators rescaled
-            float tm = fmaxf(mx, __shfl_xor(mx, 16));
-            tm = fmaxf(tm, __shfl_xor(tm, 32));
-            const float m_new = fmaxf(m_ref, tm);
-            const float alpha = fast_exp2(m_ref - m_new);
-            m_ref = m_new;
-            // O rows are q heads 4g + e: fetch their factors from the lanes that own those columns
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float a = __shfl(alpha, 4 * g + e);
-                Lacc[e] *= a;
-#pragma unroll
-                for (int nb = 0; nb < 8; ++nb) O[nb][e] *= a;
-            }
-        }
+        if (__any(mx > m_ref + 8.f)) i4_raise_ref(mx, m_ref, O, g, &Lacc);
         u32x4 pw;
         {
             float p[8];
 #pragma unroll
-#if DUO_I4_PROBE & 1     // ablation build: no transcendental (a bounded stand-in for the probability)
-            for (int i = 0; i < 8; ++i) p[i] = __builtin_amdgcn_fmed3f(fmaf(sv[i], c_, -m_ref), 0.f, 1.f);
-#else
             for (int i = 0; i < 8; ++i) p[i] = fast_exp2(fmaf(sv[i], c_, -m_ref));
-#endif
             pw.x = cvt_pk_f16(p[0], p[1]);
             pw.y = cvt_pk_f16(p[2], p[3]);
             pw.z = cvt_pk_f16(p[4], p[5]);
@@ -835,53 +828,10 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
         // row sums of the (fp16-rounded) probabilities: one more MFMA against a block of ones
         Lacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(pA, ones, Lacc, 0, 0, 0);
 
-        // ---- O += P . V^ : transpose reads two dim blocks at a time, one batch ahead of the MFMAs ------
-        u32x2 va[4], vb[4];
-        __builtin_amdgcn_sched_barrier(0);
-#if DUO_I4_PROBE & 8     // ablation build: no LDS round trip, the MFMAs of P . V^ take the packed words as they are
-        {
-            const u32x4 g0 = {T.vw[0].x & 0x3bff3bffu, T.vw[0].y & 0x3bff3bffu, T.vw[0].z & 0x3bff3bffu, T.vw[0].w & 0x3bff3bffu};
-            const u32x4 g1 = {T.vw[1].x & 0x3bff3bffu, T.vw[1].y & 0x3bff3bffu, T.vw[1].z & 0x3bff3bffu, T.vw[1].w & 0x3bff3bffu};
-#pragma unroll
-            for (int nb = 0; nb < 8; ++nb)
-                O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pA, as_f16x8((nb & 1) ? g1 : g0), O[nb], 0, 0, 0);
-            (void)va; (void)vb;
-            return;
-        }
-#endif
-#define DUO_I4_TR_BATCH(buf, nb0)                                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                              \
-        uint32_t a_ = ra ^ (uint32_t)(((nb0) + i_) << 5);                           \
-        if constexpr (MINW == 4) /* recomputed at every use: eight hoisted copies would be eight registers too many */ \
-            asm volatile("v_xor_b32 %0, %1, %2" : "=v"(a_) : "v"(ra), "v"((uint32_t)(((nb0) + i_) << 5)));           \
-        DUO_I4_TR_READ(buf[2 * i_], a_, 0);                                         \
-        DUO_I4_TR_READ(buf[2 * i_ + 1], a_, 4096);                                  \
-    }
-#define DUO_I4_PV(buf, nb0)                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                   \
-        const u32x4 w_ = {buf[2 * i_].x, buf[2 * i_].y, buf[2 * i_ + 1].x, buf[2 * i_ + 1].y};           \
-        O[(nb0) + i_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pA, as_f16x8(w_), O[(nb0) + i_], 0, 0, 0); \
-    }
-#define DUO_I4_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-        DUO_I4_TR_BATCH(va, 0);
-        DUO_I4_TR_BATCH(vb, 2);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(va, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        DUO_I4_TR_BATCH(va, 4);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(vb, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        DUO_I4_TR_BATCH(vb, 6);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(va, 4);
-        DUO_I4_WAIT(0);
-        DUO_I4_PV(vb, 6);
-#undef DUO_I4_TR_BATCH
-#undef DUO_I4_PV
-#undef DUO_I4_WAIT
+        // ---- O += P . V^ --------------------------------------------------------------------------
+        i4_pv(pA, ra, O);
     };
-    // Whole tile (two- and three-wave forms: both halves of a tile arrive together and share one vote).
+    // Whole tile: both halves of a tile arrive together and share one vote.
     auto process = [&](const I4Tile &T, int t, auto fast_tag, auto tail_tag) __attribute__((always_inline)) {
         if (P.flags & 32u) {   // debug: consume the loads, skip the arithmetic
             m_ref += __uint_as_float((T.kw[0].x ^ T.kw[1].y ^ T.vw[0].z ^ T.vw[1].w ^ T.ks[0] ^ T.ks[1] ^ T.vs[0] ^ T.vs[1]) & 1u);
@@ -890,52 +840,8 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
         f32x4 S[2];
         process_k(T, S, fast_tag);
         v_to_lds(T, fast_tag);
-        softmax_pv(T, t, S, tail_tag);
+        softmax_pv(t, S, tail_tag);
     };
-    // FOUR waves per SIMD (MINW == 4: 128 registers per wave): ONE tile buffer, refilled half by half — the K half of tile
-    // t + 32 is requested as soon as S(t) has consumed K(t), the V half as soon as P.V(t) has consumed V(t) — so four loads
-    // are in flight at every use and every wait is vmcnt(4).  A wave has half a tile of fetch lead instead of a whole one;
-    // the fourth wave of the SIMD covers the difference (round 6: the three-wave form keeps two tile buffers = 144 VGPRs;
-    // the 16 registers above 128 were exactly one half-tile).  The scale vote is taken per half (K scales before S, V
-    // scales before the LDS write), so a tile whose rows fail it takes the exact form for that half only — no reload.
-    if constexpr (MINW == 4) {
-        if (w0 < w1) {
-            using T_ = std::true_type;
-            using F_ = std::false_type;
-            I4Tile X;
-            load_half(w0, X, T_{});
-            load_half(w0, X, F_{});
-            if (P.flags & 32u) {   // debug: consume the loads, skip the arithmetic (a loop of its own: a second path through
-                                   // the main loop would make the tile registers meet through copies, i.e. through vmcnt(0))
-                for (int t = w0; t < w1; t += 32) {
-                    m_ref += __uint_as_float((X.kw[0].x ^ X.kw[1].y ^ X.ks[0] ^ X.ks[1]) & 1u);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_half(t + 32, X, T_{});
-                    __builtin_amdgcn_sched_barrier(0);
-                    m_ref += __uint_as_float((X.vw[0].z ^ X.vw[1].w ^ X.vs[0] ^ X.vs[1]) & 1u);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_half(t + 32, X, F_{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                for (int t = w0; t < w1; t += 32) {
-                    const bool tail = t + 32 > w1;
-                    f32x4 S[2];
-                    if (MODE == 1 && __all(scales_in_fma_range(X.ks[0], X.ks[1], X.ks[0], X.ks[1]))) process_k(X, S, T_{});
-                    else process_k(X, S, F_{});
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_half(t + 32, X, T_{});
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (MODE == 1 && __all(scales_in_fma_range(X.vs[0], X.vs[1], X.vs[0], X.vs[1]))) v_to_lds(X, T_{});
-                    else v_to_lds(X, F_{});
-                    softmax_pv(X, t, S, tail);
-                    __builtin_amdgcn_sched_barrier(0);
-                    load_half(t + 32, X, F_{});
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    } else {
     // Main loop over the full tiles: straight-line code with a fixed number of loads in flight (the next
     // tile's 8 loads are issued, unconditionally, before the current tile is touched; after the last full
     // tile the prefetch re-reads it) so every wait is vmcnt(8), never vmcnt(0).  It runs the FAST body and
@@ -947,20 +853,20 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
         const int t_full_end = w0 + (((w1 - w0) >> 5) << 5);   // end of the full tiles
         int t = w0;
         while (t < w1) {
-            if (MODE != 0 && t < t_full_end) {
+            if (t < t_full_end) {
                 const int t_last = t_full_end - 32;
                 I4Tile A, B;
                 load_full(t, A);
                 for (;;) {
                     load_full(min(t + 32, t_last), B);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (MODE == 1 && !__all(scales_in_fma_range(A.ks[0], A.ks[1], A.vs[0], A.vs[1]))) break;
+                    if (!__all(scales_in_fma_range(A.ks[0], A.ks[1], A.vs[0], A.vs[1]))) break;
                     process(A, t, T_{}, F_{});
                     t += 32;
                     if (t > t_last) break;
                     load_full(min(t + 32, t_last), A);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (MODE == 1 && !__all(scales_in_fma_range(B.ks[0], B.ks[1], B.vs[0], B.vs[1]))) break;
+                    if (!__all(scales_in_fma_range(B.ks[0], B.ks[1], B.vs[0], B.vs[1]))) break;
                     process(B, t, T_{}, F_{});
                     t += 32;
                     if (t > t_last) break;
@@ -978,7 +884,6 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
             }
             t += 32;
         }
-    }
     }
 
     // ---- combine the 4 waves through LDS ------------------------------------------------------
@@ -1065,39 +970,16 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_mfma_kernel(const I
 // Per folded 32-key tile and lane: 16 v_and + 4 shifts to build the operands of each of K and V, 16 + 16 conversions of (s, z),
 // ~70 fp32 operations for the two fix-ups, the vote and the softmax, 8 v_exp, 16 MFMAs — about 70 % of the issue slots of the
 // dequantising form.
-template <int MINW>
-__global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const Int4DecodeParams P) {
+__global__ __launch_bounds__(256, 2) void duo_int4_decode_fold_kernel(const Int4DecodeParams P) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15;    // key row inside a 16-key half / q column / dim column
     const int g = lane >> 4;    // 16-byte quarter of the packed row / k-slot group
 
-    int b = blockIdx.x;
-    const int ci = b < P.nblk_full ? 0 : 1;
-    if (ci) b -= P.nblk_full;
-    const Int4SegDev C = i4_select(P.cls[0], P.cls[1], ci != 0);
-    const int splits = ci ? P.splits[1] : P.splits[0];
-    const int kvh = b / splits;
-    const int split = b - kvh * splits;
-    const int qh0 = C.q_head_offset + kvh * P.group;
+    const I4Work W = i4_work(P, wave);
+    const int w0 = W.w0, w1 = W.w1, qh0 = W.qh0, splits = W.splits, split = W.split;
 
-    const int L = C.len;
-    const int units = (L + 63) >> 6;
-    const int uq = units / splits, ur = units - uq * splits;
-    const int u0 = split * uq + min(split, ur);
-    const int un = uq + (split < ur ? 1 : 0);
-    const int c0 = u0 << 6;
-    const int c1 = min((u0 + un) << 6, L);
-    const int per_wave = (((c1 - c0 + 3) >> 2) + 31) & ~31;   // quarter of the chunk, whole 32-key tiles
-    const int w0 = __builtin_amdgcn_readfirstlane(c0 + wave * per_wave);
-    const int w1 = __builtin_amdgcn_readfirstlane(min(w0 + per_wave, c1));
-
-    // uniform row bases of this kv head (token stride == 1 row: the launcher guarantees it) + per-lane byte offsets
-    const int64_t head_row = (int64_t)kvh * C.hs + (int64_t)blockIdx.z * C.bs;
-    const uint8_t *kq = C.kq + head_row * 64;
-    const uint8_t *vq = C.vq + head_row * 64;
-    const uint8_t *ksz = reinterpret_cast<const uint8_t *>(C.ksz) + head_row * 4;
-    const uint8_t *vsz = reinterpret_cast<const uint8_t *>(C.vsz) + head_row * 4;
+    // per-lane byte offsets inside a 32-key tile (token stride == 1 row: the launcher guarantees it)
     const uint32_t qoff0 = (uint32_t)r * 64u + g * 16, qoff1 = qoff0 + 16u * 64u;
     const uint32_t soff0 = (uint32_t)g * 16u, soff1 = soff0 + 64u;     // (s, z) of keys 4g..4g+3 / 16+4g..16+4g+3
 
@@ -1139,14 +1021,10 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
     const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)lds + wave * 8192;
     uint32_t wa[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wa[j] = lbase + r * 256 + (((4 * g + j) ^ r) << 4);
-    const int kr = 4 * g + (r >> 2);
-    const uint32_t ra = lbase + kr * 256 + ((((r >> 1) & 1) ^ (kr & 15)) << 4) + 8 * (r & 1);
+    for (int j = 0; j < 4; ++j) wa[j] = i4_lds_wa(lbase, r, g, j);
+    const uint32_t ra = i4_lds_ra(lbase, r, g);
 
-    uint32_t m0, m4, magic;
-    asm volatile("s_mov_b32 %0, 0x000f000f" : "=s"(m0));
-    asm volatile("s_mov_b32 %0, 0x00f000f0" : "=s"(m4));
-    asm volatile("v_mov_b32 %0, 0x64006400" : "=v"(magic));
+    const I4Masks K = i4_masks();
 
     // accumulators in the FOLDED scale: O = sum (p s') n 2^-24 (odd-position dims) / 2^-20 (even-position dims); an exact
     // tile's true-scale contribution is brought to it by 1 / colscale
@@ -1162,17 +1040,9 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
         u32x4 kw[2], vw[2], ks[2], vs[2];
     };
     uint32_t qo0 = qoff0, qo1 = qoff1, so0 = soff0, so1 = soff1;
-    typedef __attribute__((address_space(1))) const uint8_t gbyte_t;
-    typedef __attribute__((address_space(1))) const u32x4 gu32x4_t;
-    typedef __attribute__((address_space(1))) const uint32_t gu32_t;
-    auto ubase = [&](const uint8_t *p) __attribute__((always_inline)) {
-        const uint64_t a = (uint64_t)p;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return (gbyte_t *)(((uint64_t)hi << 32) | lo);
-    };
     auto load_full = [&](int t, FTile &T) __attribute__((always_inline)) {
-        gbyte_t *kq_t = ubase(kq + (int64_t)t * 64), *vq_t = ubase(vq + (int64_t)t * 64);
-        gbyte_t *ks_t = ubase(ksz + (int64_t)t * 4), *vs_t = ubase(vsz + (int64_t)t * 4);
+        gbyte_t *kq_t = ubase(W.kq + (int64_t)t * 64), *vq_t = ubase(W.vq + (int64_t)t * 64);
+        gbyte_t *ks_t = ubase(W.ksz + (int64_t)t * 4), *vs_t = ubase(W.vsz + (int64_t)t * 4);
         asm volatile("" : "+v"(qo0), "+v"(qo1), "+v"(so0), "+v"(so1));
         T.kw[0] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + qo0));
         T.kw[1] = __builtin_nontemporal_load(reinterpret_cast<gu32x4_t *>(kq_t + qo1));
@@ -1186,8 +1056,8 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
     // the partial last tile: rows past the range re-read the last one, element by element for the (s, z) words
     auto load_tail = [&](int t, FTile &T) __attribute__((always_inline)) {
         const int last = w1 - 1 - t;
-        gbyte_t *kq_t = ubase(kq + (int64_t)t * 64), *vq_t = ubase(vq + (int64_t)t * 64);
-        gbyte_t *ks_t = ubase(ksz + (int64_t)t * 4), *vs_t = ubase(vsz + (int64_t)t * 4);
+        gbyte_t *kq_t = ubase(W.kq + (int64_t)t * 64), *vq_t = ubase(W.vq + (int64_t)t * 64);
+        gbyte_t *ks_t = ubase(W.ksz + (int64_t)t * 4), *vs_t = ubase(W.vsz + (int64_t)t * 4);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const uint32_t q_ = (uint32_t)min(16 * h + r, last) * 64u + g * 16;
@@ -1208,7 +1078,7 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
     // n 2^-24, high-nibble pairs as n 2^-20
     auto nib = [&](uint32_t w) __attribute__((always_inline)) -> u32x4 {
         const uint32_t w8 = w >> 8;
-        return u32x4{w & m0, w & m4, w8 & m0, w8 & m4};
+        return u32x4{w & K.m0, w & K.m4, w8 & K.m0, w8 & K.m4};
     };
     auto lo_f = [](uint32_t x) __attribute__((always_inline)) { return __half2float(__ushort_as_half((unsigned short)(x & 0xffffu))); };
     auto hi_f = [](uint32_t x) __attribute__((always_inline)) { return __half2float(__ushort_as_half((unsigned short)(x >> 16))); };
@@ -1272,8 +1142,8 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int64_t row = (int64_t)t + min(16 * h + r, last);
-                krow[h] = *reinterpret_cast<const uint32_t *>(ksz + row * 4);
-                vrow[h] = *reinterpret_cast<const uint32_t *>(vsz + row * 4);
+                krow[h] = *reinterpret_cast<const uint32_t *>(W.ksz + row * 4);
+                vrow[h] = *reinterpret_cast<const uint32_t *>(W.vsz + row * 4);
             }
             f32x4 S[2];
 #pragma unroll
@@ -1283,7 +1153,7 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
                 const uint32_t kw[4] = {T.kw[h].x, T.kw[h].y, T.kw[h].z, T.kw[h].w};
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) {
-                    const u32x4 kd = P.fused ? dq8<false, true>(kw[kb], R, m0, m4, magic) : dq8<false, false>(kw[kb], R, m0, m4, magic);
+                    const u32x4 kd = P.fused ? dq8<false, true>(kw[kb], R, K) : dq8<false, false>(kw[kb], R, K);
                     S[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(kd), qX[kb], S[h], 0, 0, 0);
                 }
             }
@@ -1294,7 +1164,7 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     *(lds_u32x4 *)(uintptr_t)(wa[j] + h * 4096) =
-                        P.fused ? dq8<false, true>(vw[j], R, m0, m4, magic) : dq8<false, false>(vw[j], R, m0, m4, magic);
+                        P.fused ? dq8<false, true>(vw[j], R, K) : dq8<false, false>(vw[j], R, K);
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h)
@@ -1310,21 +1180,9 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
         }
         const float mx = fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])), fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
         if (__any(mx > m_ref + 8.f)) {
-            // raise the reference: true running maximum of every q column, accumulators rescaled
-            float tm = fmaxf(mx, __shfl_xor(mx, 16));
-            tm = fmaxf(tm, __shfl_xor(tm, 32));
-            const float m_new = fmaxf(m_ref, tm);
-            const float alpha = fast_exp2(m_ref - m_new);
-            m_ref = m_new;
+            const float alpha = i4_raise_ref(mx, m_ref, O, g);
             Lp *= alpha;            // (this lane's q column is r: its own factor)
             Zp *= alpha;
-            // O rows are q heads 4g + e: fetch their factors from the lanes that own those columns
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float a = __shfl(alpha, 4 * g + e);
-#pragma unroll
-                for (int nb = 0; nb < 8; ++nb) O[nb][e] *= a;
-            }
         }
         // ---- p; the A operand of P.V: P' = p s' (folded: the V rows' scales ride on P) or P itself (exact) ---------
         // (carrying P' as two fp16 operands, hi + lo, was built and measured: the error against the reference's values did
@@ -1355,40 +1213,8 @@ __global__ __launch_bounds__(256, MINW) void duo_int4_decode_fold_kernel(const I
 #pragma unroll
             for (int nb = 0; nb < 8; ++nb) O[nb] = O[nb] * colscale;
         }
-        // ---- O += P' . N' : transpose reads two dim blocks at a time, one batch ahead of the MFMAs -----
-        u32x2 va[4], vb[4];
-        __builtin_amdgcn_sched_barrier(0);
-#define DUO_I4_TR_BATCH(buf, nb0)                                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                              \
-        uint32_t a_ = ra ^ (uint32_t)(((nb0) + i_) << 5);                           \
-        if constexpr (MINW == 4) /* recomputed at every use: eight hoisted copies would be eight registers too many */ \
-            asm volatile("v_xor_b32 %0, %1, %2" : "=v"(a_) : "v"(ra), "v"((uint32_t)(((nb0) + i_) << 5)));           \
-        DUO_I4_TR_READ(buf[2 * i_], a_, 0);                                         \
-        DUO_I4_TR_READ(buf[2 * i_ + 1], a_, 4096);                                  \
-    }
-#define DUO_I4_PV(buf, nb0)                                                                              \
-    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                   \
-        const u32x4 w_ = {buf[2 * i_].x, buf[2 * i_].y, buf[2 * i_ + 1].x, buf[2 * i_ + 1].y};           \
-        O[(nb0) + i_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pA, as_f16x8(w_), O[(nb0) + i_], 0, 0, 0); \
-    }
-#define DUO_I4_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-        DUO_I4_TR_BATCH(va, 0);
-        DUO_I4_TR_BATCH(vb, 2);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(va, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        DUO_I4_TR_BATCH(va, 4);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(vb, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        DUO_I4_TR_BATCH(vb, 6);
-        DUO_I4_WAIT(4);
-        DUO_I4_PV(va, 4);
-        DUO_I4_WAIT(0);
-        DUO_I4_PV(vb, 6);
-#undef DUO_I4_TR_BATCH
-#undef DUO_I4_PV
-#undef DUO_I4_WAIT
+        // ---- O += P' . N' -------------------------------------------------------------------------
+        i4_pv(pA, ra, O);
         if (exact) {                // ... and go back to the folded one (exact powers of two both ways)
 #pragma unroll
             for (int nb = 0; nb < 8; ++nb) O[nb] = O[nb] * colinv;
@@ -1707,21 +1533,14 @@ extern "C" int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_s
     // matrix-core form for GQA groups up to 16 q heads per kv head; debug flag bit 4 (and wider groups)
     // select the scalar-FMA kernel
     const bool mfma = group <= 16 && !(duo_get_debug_flags() & 16u);
-    // waves per SIMD (= workgroups per CU) the matrix-core kernels are built and launched for.  The dequantising kernel
-    // needs 144 VGPRs, so THREE fit (512 / 3 = 170) without a spill: round 4, same box, kernel alone at 1 M context
-    // 116 -> 106 us, the 32-layer step at 3.3 M 11.49 -> 11.25 ms (round 3 ran two; four spill).  The folded kernel holds two
-    // sets of Q fragments and the tile's (scale, zero) in fp32 — 228 VGPRs — and stays at two.  DUO_INT4_DECODE_WAVES overrides.
-    static const int occ_env = [] {
-        const char *e = getenv("DUO_INT4_DECODE_WAVES");
-        const int x = e ? atoi(e) : 0;
-        return (x >= 2 && x <= 4) ? x : 0;
-    }();
+    // waves per SIMD (= workgroups per CU) of the matrix-core kernels: three for the dequantising kernel (144 VGPRs), two for
+    // the folded one (228 VGPRs) — the measured choice; the two- and four-wave trials are in profiles/r4_int4_fold.md and
+    // profiles/r6_int4_w4.md (r6_int4_w4_kernel.txt, r6_int4_w4_step.txt)
     bool folded = mfma && fused >= 2 && !(duo_get_debug_flags() & 2048u);
     for (int c = 0; c < 2; ++c)
         if (P.cls[c].n_kv_heads > 0 && P.cls[c].ts != 1) folded = false;       // the folded form needs head-major pools
-    const int occ = occ_env ? occ_env : (folded ? 2 : 3);
     // one resident round: 256 CUs x (workgroups per CU = waves per SIMD of the kernel in use)
-    const int target = std::max(1, 256 * (mfma ? occ : 2) / n_batch);      // one resident round over all batch rows
+    const int target = std::max(1, 256 * (mfma ? (folded ? 2 : 3) : 2) / n_batch);      // one resident round over all batch rows
     i4_choose_splits(P.cls[1].n_kv_heads, P.cls[1].len, ms, P.cls[0].n_kv_heads > 0 ? P.cls[1].n_kv_heads : target, P.splits[1]);
     i4_choose_splits(P.cls[0].n_kv_heads, P.cls[0].len, ms,
                      std::max(target - P.cls[1].n_kv_heads * P.splits[1], P.cls[0].n_kv_heads), P.splits[0]);
@@ -1735,33 +1554,15 @@ extern "C" int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_s
     const int nblk = P.nblk_full + P.cls[1].n_kv_heads * P.splits[1];
     hipStream_t st = (hipStream_t)stream;
     if (mfma) {
-        static const int mode = [] {
-            const char *e = getenv("DUO_INT4_DECODE_MODE");    // 0: always the 3-instruction form; 1: voted fma form (default)
-            const int x = e ? atoi(e) : 1;
-            return x == 0 ? 0 : 1;
-        }();
         dim3 grid(nblk, 1, n_batch), block(256);
         // fused >= 2: the folded form (no per-element dequantisation; `folded` above) — pools in another layout, and debug
         // bit 11, take the dequantising kernel in the (fused & 1) form
         if (folded) {
-            if (occ == 2) hipLaunchKernelGGL(duo_int4_decode_fold_kernel<2>, grid, block, 0, st, P);
-            else if (occ == 4) hipLaunchKernelGGL(duo_int4_decode_fold_kernel<4>, grid, block, 0, st, P);
-            else hipLaunchKernelGGL(duo_int4_decode_fold_kernel<3>, grid, block, 0, st, P);
+            hipLaunchKernelGGL(duo_int4_decode_fold_kernel, grid, block, 0, st, P);
+        } else if (P.fused) {
+            hipLaunchKernelGGL(duo_int4_decode_mfma_kernel<true>, grid, block, 0, st, P);
         } else {
-#define DUO_I4_LAUNCH(W_)                                                                                          \
-    do {                                                                                                           \
-        if (P.fused) {                                                                                             \
-            if (mode == 0) hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<W_, 0, true>), grid, block, 0, st, P);  \
-            else hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<W_, 1, true>), grid, block, 0, st, P);            \
-        } else {                                                                                                   \
-            if (mode == 0) hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<W_, 0, false>), grid, block, 0, st, P); \
-            else hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<W_, 1, false>), grid, block, 0, st, P);           \
-        }                                                                                                          \
-    } while (0)
-        if (occ == 2) DUO_I4_LAUNCH(2);
-        else if (occ == 4) DUO_I4_LAUNCH(4);
-        else DUO_I4_LAUNCH(3);
-#undef DUO_I4_LAUNCH
+            hipLaunchKernelGGL(duo_int4_decode_mfma_kernel<false>, grid, block, 0, st, P);
         }
     } else {
         const int gt = (group % 4 == 0) ? 4 : (group % 2 == 0) ? 2 : 1;
