@@ -247,6 +247,18 @@ struct Int4DecodeParams {
     int64_t ws_row_floats;     // ... and floats between the rows' partial areas
 };
 
+// A step of n_tokens query tokens (duo_int4_decode_mfma_kernel<FUSED, true>): q / out are [B, T, Hq, 128], grid.y = column
+// block (tpb = 16 / group tokens each), the partials of (batch row b, token i) are row b * n_tokens + i of the workspace.
+struct Int4MultiParams {
+    Int4DecodeParams D;
+    int32_t n_tokens, tpb;
+    int64_t q_ts, out_ts;      // q / out elements between tokens
+};
+template <bool MULTI>
+using i4_params_t = std::conditional_t<MULTI, Int4MultiParams, Int4DecodeParams>;
+__device__ __forceinline__ const Int4DecodeParams &i4_base(const Int4DecodeParams &P) { return P; }
+__device__ __forceinline__ const Int4DecodeParams &i4_base(const Int4MultiParams &P) { return P.D; }
+
 __device__ __forceinline__ Int4SegDev i4_select(const Int4SegDev &a, const Int4SegDev &b, bool pb) {
     Int4SegDev r;
     r.kq = pb ? b.kq : a.kq; r.vq = pb ? b.vq : a.vq;
@@ -692,8 +704,18 @@ __device__ __forceinline__ float i4_raise_ref(float mx, float &m_ref, f32x4 (&O)
 
 // FUSED: fma(n, s, z) instead of hadd(hmul(n, s), z) (see dq8).  Tiles whose scales allow it (wave vote) take the masked
 // exact-fma form, the others the always-exact shifted form.
-template <bool FUSED>
-__global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4DecodeParams P) {
+// MULTI: a step of T query tokens against pools that already hold the step's T rows at their ends (demo/w8a8kv4_llama.py:
+// 239-274 for q_len > 1).  The 16 columns of the Q^T fragments, of which a single token fills `group`, carry tpb = 16 / group
+// tokens: column c = (token tok0 + c / group, q head qh0 + c % group), tok0 = blockIdx.y * tpb — one pass over the pool for up
+// to tpb tokens.  Bottom-right causal: column c sees key j iff j <= len - T + token(c).  Tiles that end at or before row
+// len - T + tok0 are visible to every column and run the single-token body as it is; the (at most ceil(T / 32) + 1) tiles behind
+// them take the general dequantisation and an element mask by SELECTION: a masked probability is the constant 0, and a column
+// without a visible key in a tile takes no part in the vote, so a column that sees nothing in this wave's key range (the last
+// wave of a split often holds only the step's own rows) leaves it with m = sentinel, l = 0, O = 0 and gets weight
+// exp2(sentinel - M) = 0 in the LDS combine and in the merge.
+template <bool FUSED, bool MULTI = false>
+__global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const i4_params_t<MULTI> PP) {
+    const Int4DecodeParams &P = i4_base(PP);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15;    // key row inside a 16-key half / q column / dim column
@@ -708,13 +730,30 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
     const uint32_t qoff0 = (uint32_t)r * row_b + g * 16, qoff1 = qoff0 + 16u * row_b;
     const uint32_t soff0 = (uint32_t)r * sz_b, soff1 = soff0 + 16u * sz_b;
 
+    // MULTI: this lane's column — its token and q head, whether it is a column of the step at all, and the last key it sees
+    // inside this wave's range (padding columns multiply zeros and see everything, like the single-token kernel's)
+    int tok0 = 0, lim_w = 0;
+    bool col = false;
+    const __half *qcol = nullptr;
+    if constexpr (MULTI) {
+        tok0 = blockIdx.y * PP.tpb;
+        const int tl = r / P.group, tok = tok0 + tl;
+        col = tl < PP.tpb && tok < PP.n_tokens;
+        qcol = P.q + (int64_t)blockIdx.z * P.q_bs + (int64_t)tok * PP.q_ts + (int64_t)(qh0 + r - tl * P.group) * P.q_head_stride;
+        lim_w = col ? min(w1 - 1, W.C.len - PP.n_tokens + tok) : w1 - 1;
+    }
+
     // Q^T fragments: column r = q head qh0 + r (zero beyond the group), dims 32g + 8kb + [1,5,0,4,3,7,2,6]
     f16x8_t qB[4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
         u32x4 w = {0u, 0u, 0u, 0u};
-        if (r < P.group)
-            w = *reinterpret_cast<const u32x4 *>(P.q + (int64_t)blockIdx.z * P.q_bs + (int64_t)(qh0 + r) * P.q_head_stride + 32 * g + 8 * kb);
+        if constexpr (MULTI) {
+            if (col) w = *reinterpret_cast<const u32x4 *>(qcol + 32 * g + 8 * kb);
+        } else {
+            if (r < P.group)
+                w = *reinterpret_cast<const u32x4 *>(P.q + (int64_t)blockIdx.z * P.q_bs + (int64_t)(qh0 + r) * P.q_head_stride + 32 * g + 8 * kb);
+        }
         // w = (d0 d1)(d2 d3)(d4 d5)(d6 d7), low half first
         u32x4 o;
         o.x = (w.x >> 16) | (w.z & 0xffff0000u);          // d1, d5
@@ -783,8 +822,8 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
                 S[h] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(dq8<FAST, FUSED>(kw[kb], R, K)), qB[kb], S[h], 0, 0, 0);
         }
     };
-    // V half: V^ -> LDS, then (softmax_pv) softmax of S against the reference maximum and O += P . V^.  TAIL: partial tile,
-    // keys past the range masked.
+    // V half: V^ -> LDS, then (softmax_pv) softmax of S against the reference maximum and O += P . V^.  MODE 1: partial tile,
+    // keys past the range masked; MODE 2 (MULTI): keys past the range or past the column's causal limit masked by selection.
     auto v_to_lds = [&](const I4Tile &T, auto fast_tag) __attribute__((always_inline)) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // ---- V^ -> LDS (issued early: the writes drain while the softmax runs) -----------------
@@ -796,8 +835,9 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
             for (int j = 0; j < 4; ++j) *(lds_u32x4 *)(uintptr_t)(wa[j] + h * 4096) = dq8<FAST, FUSED>(vw[j], R, K);
         }
     };
-    auto softmax_pv = [&](int t, const f32x4 (&S)[2], auto tail_tag) __attribute__((always_inline)) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
+    auto softmax_pv = [&](int t, const f32x4 (&S)[2], auto mode_tag) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        constexpr bool TAIL = MODE == 1;
         // ---- softmax against the reference maximum ---------------------------------------------
         float sv[8];
 #pragma unroll
@@ -811,14 +851,33 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
                 for (int e = 0; e < 4; ++e)
                     if (t + 16 * h + 4 * g + e >= w1) sv[4 * h + e] = kNegSentinelI4;
         }
-        const float mx = c_ * fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])),
-                                    fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
+        bool vis[8];
+        float mx;
+        if constexpr (MODE == 2) {
+            // a column without a visible key votes with the sentinel itself (not c_ x sentinel, which exceeds it) and so
+            // neither triggers the raise nor moves its reference
+            float sm[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    vis[4 * h + e] = t + 16 * h + 4 * g + e <= lim_w;
+                    sm[4 * h + e] = vis[4 * h + e] ? sv[4 * h + e] * c_ : kNegSentinelI4;
+                }
+            mx = fmaxf(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])), fmaxf(fmaxf(sm[4], sm[5]), fmaxf(sm[6], sm[7])));
+        } else {
+            mx = c_ * fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])),
+                            fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
+        }
         if (__any(mx > m_ref + 8.f)) i4_raise_ref(mx, m_ref, O, g, &Lacc);
         u32x4 pw;
         {
             float p[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) p[i] = fast_exp2(fmaf(sv[i], c_, -m_ref));
+            for (int i = 0; i < 8; ++i) {
+                p[i] = fast_exp2(fmaf(sv[i], c_, -m_ref));
+                if constexpr (MODE == 2) p[i] = vis[i] ? p[i] : 0.f;
+            }
             pw.x = cvt_pk_f16(p[0], p[1]);
             pw.y = cvt_pk_f16(p[2], p[3]);
             pw.z = cvt_pk_f16(p[4], p[5]);
@@ -832,7 +891,7 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
         i4_pv(pA, ra, O);
     };
     // Whole tile: both halves of a tile arrive together and share one vote.
-    auto process = [&](const I4Tile &T, int t, auto fast_tag, auto tail_tag) __attribute__((always_inline)) {
+    auto process = [&](const I4Tile &T, int t, auto fast_tag, auto mode_tag) __attribute__((always_inline)) {
         if (P.flags & 32u) {   // debug: consume the loads, skip the arithmetic
             m_ref += __uint_as_float((T.kw[0].x ^ T.kw[1].y ^ T.vw[0].z ^ T.vw[1].w ^ T.ks[0] ^ T.ks[1] ^ T.vs[0] ^ T.vs[1]) & 1u);
             return;
@@ -840,19 +899,24 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
         f32x4 S[2];
         process_k(T, S, fast_tag);
         v_to_lds(T, fast_tag);
-        softmax_pv(t, S, tail_tag);
+        softmax_pv(t, S, mode_tag);
     };
     // Main loop over the full tiles: straight-line code with a fixed number of loads in flight (the next
     // tile's 8 loads are issued, unconditionally, before the current tile is touched; after the last full
     // tile the prefetch re-reads it) so every wait is vmcnt(8), never vmcnt(0).  It runs the FAST body and
     // is left at a tile whose rows fail the scale vote: that one tile (re-loaded) goes through the
     // always-exact general form, then the fast loop resumes.  The partial last tile is general too.
-    if (w0 < w1) {
+    // MULTI: that loop ends at wE, the end of the tiles every column of this block sees whole; the masked tiles follow it.
+    int wE = w1;
+    if constexpr (MULTI) wE = w0 + ((max(min(w1, W.C.len - PP.n_tokens + tok0 + 1) - w0, 0) >> 5) << 5);
+    if (w0 < wE) {
         using T_ = std::true_type;
         using F_ = std::false_type;
-        const int t_full_end = w0 + (((w1 - w0) >> 5) << 5);   // end of the full tiles
+        using M0_ = std::integral_constant<int, 0>;
+        using M1_ = std::integral_constant<int, 1>;
+        const int t_full_end = w0 + (((wE - w0) >> 5) << 5);   // end of the full tiles
         int t = w0;
-        while (t < w1) {
+        while (t < wE) {
             if (t < t_full_end) {
                 const int t_last = t_full_end - 32;
                 I4Tile A, B;
@@ -861,28 +925,35 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
                     load_full(min(t + 32, t_last), B);
                     __builtin_amdgcn_sched_barrier(0);
                     if (!__all(scales_in_fma_range(A.ks[0], A.ks[1], A.vs[0], A.vs[1]))) break;
-                    process(A, t, T_{}, F_{});
+                    process(A, t, T_{}, M0_{});
                     t += 32;
                     if (t > t_last) break;
                     load_full(min(t + 32, t_last), A);
                     __builtin_amdgcn_sched_barrier(0);
                     if (!__all(scales_in_fma_range(B.ks[0], B.ks[1], B.vs[0], B.vs[1]))) break;
-                    process(B, t, T_{}, F_{});
+                    process(B, t, T_{}, M0_{});
                     t += 32;
                     if (t > t_last) break;
                 }
-                if (t >= w1) break;
+                if (t >= wE) break;
             }
             // one tile in the general form: the one that failed the vote, or the partial last one
             I4Tile X;
-            if (t + 32 <= w1) {
+            if (MULTI || t + 32 <= wE) {
                 load_full(t, X);
-                process(X, t, F_{}, F_{});
+                process(X, t, F_{}, M0_{});
             } else {
                 load_tail(t, X);
-                process(X, t, F_{}, T_{});
+                process(X, t, F_{}, M1_{});
             }
             t += 32;
+        }
+    }
+    if constexpr (MULTI) {
+        for (int t = wE; t < w1; t += 32) {
+            I4Tile X;
+            load_tail(t, X);
+            process(X, t, std::false_type{}, std::integral_constant<int, 2>{});
         }
     }
 
@@ -906,7 +977,9 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
         }
     }
     __syncthreads();
-    for (int idx = threadIdx.x; idx < P.group * DUO_HEAD_DIM; idx += 256) {
+    int n_cols = P.group;
+    if constexpr (MULTI) n_cols = min(PP.tpb, PP.n_tokens - tok0) * P.group;      // the step's columns in this block
+    for (int idx = threadIdx.x; idx < n_cols * DUO_HEAD_DIM; idx += 256) {
         const int q = idx >> 7;
         const int d = idx & 127;
         float M = s_ml[0][q][0];
@@ -919,15 +992,22 @@ __global__ __launch_bounds__(256, 3) void duo_int4_decode_mfma_kernel(const Int4
             Lsum = fmaf(s_ml[w][q][1], sc, Lsum);
             o = fmaf(s_acc[(w * 16 + q) * DUO_HEAD_DIM + d], sc, o);
         }
-        const int qh = qh0 + q;
+        int qh = qh0 + q;
+        int64_t out_row = (int64_t)blockIdx.z * P.out_bs, ws_row = blockIdx.z;
+        if constexpr (MULTI) {
+            const int tl = q / P.group, tok = tok0 + tl;
+            qh = qh0 + q - tl * P.group;
+            out_row += (int64_t)tok * PP.out_ts;
+            ws_row = (int64_t)blockIdx.z * PP.n_tokens + tok;
+        }
         if (splits == 1) {
-            P.out[(int64_t)blockIdx.z * P.out_bs + (int64_t)qh * P.out_head_stride + d] = __float2half(o / Lsum);
+            P.out[out_row + (int64_t)qh * P.out_head_stride + d] = __float2half(o / Lsum);
         } else {
             const int64_t slot = (int64_t)qh * P.max_splits + split;
-            P.ws_acc[(int64_t)blockIdx.z * P.ws_row_floats + slot * DUO_HEAD_DIM + d] = o;
+            P.ws_acc[ws_row * P.ws_row_floats + slot * DUO_HEAD_DIM + d] = o;
             if (d == 0) {
-                P.ws_ml[(int64_t)blockIdx.z * P.ws_row_floats + slot * 2 + 0] = M;
-                P.ws_ml[(int64_t)blockIdx.z * P.ws_row_floats + slot * 2 + 1] = Lsum;
+                P.ws_ml[ws_row * P.ws_row_floats + slot * 2 + 0] = M;
+                P.ws_ml[ws_row * P.ws_row_floats + slot * 2 + 1] = Lsum;
             }
         }
     }
@@ -1482,6 +1562,41 @@ static void i4_choose_splits(int n_kv_heads, int L, int max_splits, int budget, 
     splits = std::max(1, std::min(s, std::min(units, max_splits)));
 }
 
+// the two head classes of a decode launch from the caller's pools (every present pool holds at least min_len rows); returns
+// the q heads they cover, or a negative error code
+static int i4_set_classes(Int4DecodeParams &P, const duo_int4_pool *full, const duo_int4_pool *stream_cls, int group,
+                          int min_len) {
+    const duo_int4_pool *src[2] = {full, stream_cls};
+    int n_q_heads = 0;
+    for (int c = 0; c < 2; ++c) {
+        Int4SegDev &S = P.cls[c];
+        S = Int4SegDev{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
+        if (!src[c] || src[c]->n_kv_heads <= 0) continue;
+        const duo_int4_pool &p = *src[c];
+        if (!p.k_q || !p.v_q || !p.k_sz || !p.v_sz || p.len < min_len) return DUO_EINVAL;
+        S = Int4SegDev{(const uint8_t *)p.k_q, (const uint8_t *)p.v_q, (const __half *)p.k_sz, (const __half *)p.v_sz,
+                       p.token_stride_rows, p.head_stride_rows, p.len, p.n_kv_heads, p.q_head_offset, p.batch_stride_rows};
+        n_q_heads += p.n_kv_heads * group;
+    }
+    return n_q_heads;
+}
+// the merge of the classes that were split, over P's partials
+static Int4MergeParams i4_merge_params(const Int4DecodeParams &P, int &n_merge) {
+    Int4MergeParams M;
+    M.ws_ml = P.ws_ml; M.ws_acc = P.ws_acc; M.out = P.out; M.out_head_stride = P.out_head_stride;
+    M.max_splits = P.max_splits;
+    M.ws_row_floats = P.ws_row_floats;
+    M.out_bs = P.out_bs;
+    n_merge = 0;
+    for (int c = 0; c < 2; ++c) {
+        M.qh_begin[c] = P.cls[c].q_head_offset;
+        M.qh_end[c] = P.cls[c].q_head_offset + P.cls[c].n_kv_heads * P.group;
+        M.splits[c] = P.splits[c];
+        if (P.splits[c] > 1) n_merge += P.cls[c].n_kv_heads * P.group;
+    }
+    return M;
+}
+
 extern "C" int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_stride, int64_t q_head_stride, void *out,
                                                 int64_t out_batch_stride, int64_t out_head_stride, int32_t n_batch,
                                                 int32_t group, const duo_int4_pool *full,
@@ -1511,19 +1626,8 @@ extern "C" int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_s
     P.out_bs = out_batch_stride;
     P.q = (const __half *)q; P.q_head_stride = q_head_stride;
     P.out = (__half *)out; P.out_head_stride = out_head_stride;
-    const duo_int4_pool *src[2] = {full, stream_cls};
-    int n_q_heads = 0;
-    for (int c = 0; c < 2; ++c) {
-        Int4SegDev &S = P.cls[c];
-        S = Int4SegDev{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0};
-        if (!src[c] || src[c]->n_kv_heads <= 0) continue;
-        const duo_int4_pool &p = *src[c];
-        if (!p.k_q || !p.v_q || !p.k_sz || !p.v_sz || p.len <= 0) return DUO_EINVAL;
-        S = Int4SegDev{(const uint8_t *)p.k_q, (const uint8_t *)p.v_q, (const __half *)p.k_sz, (const __half *)p.v_sz,
-                       p.token_stride_rows, p.head_stride_rows, p.len, p.n_kv_heads, p.q_head_offset, p.batch_stride_rows};
-        n_q_heads += p.n_kv_heads * group;
-    }
-    if (n_q_heads <= 0) return 0;
+    const int n_q_heads = i4_set_classes(P, full, stream_cls, group, 1);
+    if (n_q_heads <= 0) return n_q_heads;
     P.group = group;
     P.flags = duo_get_debug_flags();
     P.scale_log2e = scale * 1.4426950408889634f;
@@ -1572,22 +1676,105 @@ extern "C" int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_s
         else hipLaunchKernelGGL(duo_int4_decode_split_kernel<1>, grid, block, 0, st, P);
     }
     DUO_HIP_CHECK_LAUNCH();
-    Int4MergeParams M;
-    M.ws_ml = P.ws_ml; M.ws_acc = P.ws_acc; M.out = P.out; M.out_head_stride = out_head_stride;
-    M.max_splits = P.max_splits;
-    M.ws_row_floats = P.ws_row_floats;
-    M.out_bs = out_batch_stride;
-    int n_merge = 0;
-    for (int c = 0; c < 2; ++c) {
-        M.qh_begin[c] = P.cls[c].q_head_offset;
-        M.qh_end[c] = P.cls[c].q_head_offset + P.cls[c].n_kv_heads * group;
-        M.splits[c] = P.splits[c];
-        if (P.splits[c] > 1) n_merge += P.cls[c].n_kv_heads * group;
-    }
+    int n_merge;
+    const Int4MergeParams M = i4_merge_params(P, n_merge);
     // debug flag bit 1: leave the partials unmerged (a HIP-event pair then brackets the split kernel alone)
     if (n_merge > 0 && !(duo_get_debug_flags() & 2u)) {
         hipLaunchKernelGGL(duo_int4_decode_merge_kernel, dim3(n_merge, 4, n_batch), dim3(256), 0, st, M);
         DUO_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// ---- a step of n_tokens query tokens over the packed pools (ABI v8) ------------------------------------------------------
+extern "C" int duo_attn_decode_int4_multi_batched_f16(const void *q, int64_t q_batch_stride, int64_t q_token_stride,
+                                                      int64_t q_head_stride, void *out, int64_t out_batch_stride,
+                                                      int64_t out_token_stride, int64_t out_head_stride, int32_t n_batch,
+                                                      int32_t n_tokens, int32_t group, const duo_int4_pool *full,
+                                                      const duo_int4_pool *stream_cls, float scale, int32_t head_dim,
+                                                      int32_t fused, void *workspace, int64_t workspace_bytes, void *stream);
+extern "C" int duo_attn_decode_int4_multi_f16(const void *q, int64_t q_token_stride, int64_t q_head_stride, void *out,
+                                              int64_t out_token_stride, int64_t out_head_stride, int32_t n_tokens,
+                                              int32_t group, const duo_int4_pool *full, const duo_int4_pool *stream_cls,
+                                              float scale, int32_t head_dim, int32_t fused, void *workspace,
+                                              int64_t workspace_bytes, void *stream) {
+    return duo_attn_decode_int4_multi_batched_f16(q, 0, q_token_stride, q_head_stride, out, 0, out_token_stride,
+                                                  out_head_stride, 1, n_tokens, group, full, stream_cls, scale, head_dim,
+                                                  fused, workspace, workspace_bytes, stream);
+}
+// q / out [B, T, n_q_heads, 128] fp16; grid = (kv head x split, column block of 16 / group tokens, batch row)
+extern "C" int duo_attn_decode_int4_multi_batched_f16(const void *q, int64_t q_batch_stride, int64_t q_token_stride,
+                                                      int64_t q_head_stride, void *out, int64_t out_batch_stride,
+                                                      int64_t out_token_stride, int64_t out_head_stride, int32_t n_batch,
+                                                      int32_t n_tokens, int32_t group, const duo_int4_pool *full,
+                                                      const duo_int4_pool *stream_cls, float scale, int32_t head_dim,
+                                                      int32_t fused, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (head_dim != DUO_HEAD_DIM) return DUO_EHEADDIM;
+    if (!q || !out || group <= 0 || n_batch < 0 || n_tokens < 1 || n_tokens > 64 || (int64_t)n_batch * n_tokens > 65535)
+        return DUO_EINVAL;
+    if (group > 16) return DUO_EGROUP;      // the matrix-core form only: 16 columns hold at least one token's q heads
+    if (fused < 0 || fused > 3) return DUO_EINVAL;
+    if (n_tokens == 1)
+        return duo_attn_decode_int4_batched_f16(q, q_batch_stride, q_head_stride, out, out_batch_stride, out_head_stride,
+                                                n_batch, group, full, stream_cls, scale, head_dim, fused, workspace,
+                                                workspace_bytes, stream);
+    if (n_batch == 0) return 0;
+    if (((q_token_stride | q_head_stride) & 7) || ((out_token_stride | out_head_stride) & 3)) return DUO_EINVAL;
+    if (n_batch > 1 && ((q_batch_stride & 7) || (out_batch_stride & 3))) return DUO_EINVAL;
+    Int4MultiParams MP;
+    Int4DecodeParams &P = MP.D;
+    P.fused = fused & 1;        // modes 2 / 3: there is no folded multi-token form, the dequantising form (fused & 1) runs
+    P.q_bs = q_batch_stride;
+    P.out_bs = out_batch_stride;
+    P.q = (const __half *)q; P.q_head_stride = q_head_stride;
+    P.out = (__half *)out; P.out_head_stride = out_head_stride;
+    const int n_q_heads = i4_set_classes(P, full, stream_cls, group, n_tokens);     // every token sees >= 1 row: len >= T
+    if (n_q_heads <= 0) return n_q_heads;
+    P.group = group;
+    P.flags = duo_get_debug_flags();
+    P.scale_log2e = scale * 1.4426950408889634f;
+    MP.n_tokens = n_tokens;
+    MP.tpb = 16 / group;
+    MP.q_ts = q_token_stride;
+    MP.out_ts = out_token_stride;
+    const int n_cb = (n_tokens + MP.tpb - 1) / MP.tpb;      // column blocks: each reads its kv head's rows once
+    const int64_t n_rows = (int64_t)n_batch * n_tokens;     // partial areas: one per (batch row, token)
+    const int64_t per_split = (int64_t)n_q_heads * (DUO_HEAD_DIM + 2) * (int64_t)sizeof(float) * n_rows;
+    const int max_splits = workspace ? (int)std::min<int64_t>(workspace_bytes / per_split, 1024) : 0;
+    const int ms = max_splits > 0 ? max_splits : 1;
+    // one resident round (256 CUs x 3 workgroups) over all batch rows and column blocks
+    const int target = std::max(1, 256 * 3 / (n_batch * n_cb));
+    i4_choose_splits(P.cls[1].n_kv_heads, P.cls[1].len, ms, P.cls[0].n_kv_heads > 0 ? P.cls[1].n_kv_heads : target, P.splits[1]);
+    i4_choose_splits(P.cls[0].n_kv_heads, P.cls[0].len, ms,
+                     std::max(target - P.cls[1].n_kv_heads * P.splits[1], P.cls[0].n_kv_heads), P.splits[0]);
+    const int need = std::max(P.splits[0], P.splits[1]);
+    if (need > 1 && max_splits < need) return DUO_EWORKSPC;
+    P.max_splits = need > 1 ? need : 1;
+    P.ws_ml = (float *)workspace;
+    P.ws_acc = P.ws_ml ? P.ws_ml + (int64_t)n_q_heads * P.max_splits * 2 : nullptr;
+    P.ws_row_floats = (int64_t)n_q_heads * P.max_splits * (DUO_HEAD_DIM + 2);
+    P.nblk_full = P.cls[0].n_kv_heads * P.splits[0];
+    const int nblk = P.nblk_full + P.cls[1].n_kv_heads * P.splits[1];
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(nblk, n_cb, n_batch), block(256);
+    if (P.fused) hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<true, true>), grid, block, 0, st, MP);
+    else hipLaunchKernelGGL((duo_int4_decode_mfma_kernel<false, true>), grid, block, 0, st, MP);
+    DUO_HIP_CHECK_LAUNCH();
+    // the single-token merge kernel, its batch dimension carrying (batch row, token): the partial areas are laid out that way,
+    // and so are the output rows when a batch row's tokens are out_token_stride apart all the way (else: one launch per row)
+    int n_merge;
+    Int4MergeParams M = i4_merge_params(P, n_merge);
+    M.out_bs = out_token_stride;
+    if (n_merge > 0 && !(duo_get_debug_flags() & 2u)) {
+        const bool flat = n_batch == 1 || out_batch_stride == (int64_t)n_tokens * out_token_stride;
+        for (int b = 0; b < (flat ? 1 : n_batch); ++b) {
+            hipLaunchKernelGGL(duo_int4_decode_merge_kernel, dim3(n_merge, 4, flat ? (unsigned)n_rows : (unsigned)n_tokens),
+                               dim3(256), 0, st, M);
+            DUO_HIP_CHECK_LAUNCH();
+            M.ws_ml += (int64_t)n_tokens * P.ws_row_floats;
+            M.ws_acc += (int64_t)n_tokens * P.ws_row_floats;
+            M.out += out_batch_stride;
+        }
     }
     return 0;
 }

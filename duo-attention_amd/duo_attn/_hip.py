@@ -18,7 +18,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", "libduoattn_hip.so"))
-ABI_VERSION = 7
+ABI_VERSION = 8
 HEAD_DIM = 128
 
 
@@ -266,6 +266,16 @@ _SIGNATURES = {
         ctypes.c_int,
         [c_void_p, c_int64, c_void_p, c_int64, c_int32, POINTER(Int4Pool), POINTER(Int4Pool), c_float, c_int32,
          c_int32, c_void_p, c_int64, c_void_p],
+    ),
+    "duo_attn_decode_int4_multi_f16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, POINTER(Int4Pool), POINTER(Int4Pool),
+         c_float, c_int32, c_int32, c_void_p, c_int64, c_void_p],
+    ),
+    "duo_attn_decode_int4_multi_batched_f16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,
+         POINTER(Int4Pool), POINTER(Int4Pool), c_float, c_int32, c_int32, c_void_p, c_int64, c_void_p],
     ),
     "duo_lambda_attn_fwd_bf16": (
         ctypes.c_int,
@@ -1286,6 +1296,46 @@ def attn_decode_int4_batched(q: torch.Tensor, out: torch.Tensor, group: int, ful
                                                 byref(stream) if stream is not None else None, float(scale), q.shape[2],
                                                 _int4_mode(fused), ws.data_ptr(), ws.numel() * 4, _stream_ptr()),
            "duo_attn_decode_int4_batched_f16")
+
+
+def _multi_rows(n_tokens: int) -> int:
+    """partials of a multi-token step: T x Hq slots per split, T rounded up to a power of two so that the workspaces
+    (kept per q-head count, never freed) are those of at most seven sizes"""
+    return 1 << max(0, int(n_tokens) - 1).bit_length()
+
+
+def attn_decode_int4_multi(q: torch.Tensor, out: torch.Tensor, group: int, full: Optional[Int4Pool],
+                           stream: Optional[Int4Pool], scale: float, fused=False):
+    """q, out [T, Hq, 128] fp16, 1 <= T <= 64: the attention of a T-token step over the packed pools, which already hold the
+    step's rows (both lengths >= T); token i sees rows [0, len - T + i].  ``fused``: see ``_int4_mode`` (2 / 3 run as 0 / 1)."""
+    lib = load_library()
+    _require_gpu(q, "q", torch.float16)
+    _require_gpu(out, "out", torch.float16)
+    assert q.dim() == 3 and q.stride(2) == 1 and out.shape == q.shape and out.stride(2) == 1
+    ws = decode_workspace(q.device, _multi_rows(q.shape[0]) * q.shape[1])
+    _check(lib.duo_attn_decode_int4_multi_f16(q.data_ptr(), q.stride(0), q.stride(1), out.data_ptr(), out.stride(0),
+                                              out.stride(1), q.shape[0], int(group),
+                                              byref(full) if full is not None else None,
+                                              byref(stream) if stream is not None else None, float(scale), q.shape[2],
+                                              _int4_mode(fused), ws.data_ptr(), ws.numel() * 4, _stream_ptr()),
+           "duo_attn_decode_int4_multi_f16")
+
+
+def attn_decode_int4_multi_batched(q: torch.Tensor, out: torch.Tensor, group: int, full: Optional[Int4Pool],
+                                   stream: Optional[Int4Pool], scale: float, fused=False):
+    """q, out [B, T, Hq, 128] fp16; pools built from [B, rows, h, ...] views: every batch row in one launch pair"""
+    lib = load_library()
+    _require_gpu(q, "q", torch.float16)
+    _require_gpu(out, "out", torch.float16)
+    assert q.dim() == 4 and q.stride(3) == 1 and out.shape == q.shape and out.stride(3) == 1
+    ws = decode_workspace(q.device, _multi_rows(q.shape[1]) * q.shape[2])
+    _check(lib.duo_attn_decode_int4_multi_batched_f16(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), out.data_ptr(),
+                                                      out.stride(0), out.stride(1), out.stride(2), q.shape[0], q.shape[1],
+                                                      int(group), byref(full) if full is not None else None,
+                                                      byref(stream) if stream is not None else None, float(scale),
+                                                      q.shape[3], _int4_mode(fused), ws.data_ptr(), ws.numel() * 4,
+                                                      _stream_ptr()),
+           "duo_attn_decode_int4_multi_batched_f16")
 
 
 def set_debug_flags(flags: int):

@@ -42,7 +42,8 @@ class QuantizedCache:
 
 class DuoAttentionStaticINT4KVCache:
     def __init__(self, model, full_attention_heads, batch_size, max_size, sink_size, recent_size,
-                 prefilling_chunk_size, fused_dequant: bool = False, folded_decode: bool = False):
+                 prefilling_chunk_size, fused_dequant: bool = False, folded_decode: bool = False,
+                 multi_token_decode: bool = False):
         """``fused_dequant``: dequantise as ONE fma(q, s, z) instead of the source's hmul-then-hadd (two roundings, the
         default here).  Which of the two the reference's own build computes depends on whether its compiler contracts
         ``__hadd(__hmul(f, s), z)``; both forms are pinned against builds of the reference's kernel.
@@ -53,7 +54,13 @@ class DuoAttentionStaticINT4KVCache:
         contexts; its outputs differ from the reference's by the reference's own value rounding — inside the bar that
         budgets one fp16 ulp per dequantised value, outside the strict decode bar the default meets (DESIGN §3,
         profiles/r4_int4_fold.md).  Default ``False``: every tile dequantises in registers, bit for bit the values ``get()``
-        would have written to scratch."""
+        would have written to scratch.
+        ``multi_token_decode`` (opt-in): the patched attention forward (``duo_attn.patch.int4``) sends a step of 2 ..
+        ``MULTI_TOKEN_LIMIT`` tokens against a non-empty cache to ``multi_token_attention`` — one or a few passes over the
+        packed pools — instead of ``prefill_attention``, which dequantises both whole pools to fp16 scratch first.  Same
+        function, same dequantised values (always the dequantising kernel, ``folded_decode`` or not), summed in another
+        order.  Default ``False``: such steps keep the route they had."""
+        self.multi_token_decode = bool(multi_token_decode)
         self.fused_dequant = bool(fused_dequant)
         self.folded_decode = bool(folded_decode)
         self.batch_size, self.max_size = batch_size, max_size
@@ -225,20 +232,39 @@ class DuoAttentionStaticINT4KVCache:
             be.attention(query_states[b], out[b], G, full, stream, scale)
         return out
 
+    def _pools(self, layer_idx):
+        """the layer's (retrieval, streaming) pools as the decode entry points take them, at their current lengths"""
+        nf, ns = self.num_full_kv_head_list[layer_idx], self.num_streaming_kv_head_list[layer_idx]
+        n, m = self.kv_seq_len_list[layer_idx], self.streaming_kv_seq_len_list[layer_idx]
+        fk, fv = self.full_key_caches[layer_idx], self.full_value_caches[layer_idx]
+        sk, sv = self.streaming_key_caches[layer_idx], self.streaming_value_caches[layer_idx]
+        full = _hip.make_int4_pool(fk.quantized_data, fk.scale_zero, fv.quantized_data, fv.scale_zero, n, 0) if nf else None
+        stream = _hip.make_int4_pool(sk.quantized_data, sk.scale_zero, sv.quantized_data, sv.scale_zero, m,
+                                     nf * self.num_kv_groups) if ns else None
+        return full, stream
+
+    # ---------------------------------------------------------------- multi-token step on the packed pools
+    def multi_token_attention(self, layer_idx, query_states, scale=None):
+        """query_states [B, T, Hq, 128] fp16 (after RoPE, after put()), 1 <= T <= 64, the cache non-empty before the put:
+        the later-chunk attention of reference demo/w8a8kv4_llama.py:239-274 — token i of a retrieval head over rows
+        [0, n - T + i] of the dequantised full pool, of a streaming head over rows [0, m - T + i] of the dequantised
+        streaming pool — computed on the packed pools (``duo_attn_decode_int4_multi_batched_f16``), without ``get()``'s
+        scratch.  What ``prefill_attention`` computes for the same step.  Returns [B, T, Hq, 128] fp16."""
+        full, stream = self._pools(layer_idx)
+        out = torch.empty_like(query_states)
+        scale = self.head_dim ** -0.5 if scale is None else scale
+        _hip.attn_decode_int4_multi_batched(query_states, out, self.num_kv_groups, full, stream, scale,
+                                            fused=self.fused_dequant)
+        return out
+
     # ---------------------------------------------------------------- fused decode attention
     def decode_attention(self, layer_idx, query_states, scale=None):
         """query_states [B, 1, Hq, 128] fp16 (after RoPE, after put()): attention of the decode branch
         of reference demo/w8a8kv4_llama.py:240-274 over the dequantised pools, computed on the packed
         pools.  Returns [B, 1, Hq, 128] fp16."""
-        nf, ns = self.num_full_kv_head_list[layer_idx], self.num_streaming_kv_head_list[layer_idx]
-        n, m = self.kv_seq_len_list[layer_idx], self.streaming_kv_seq_len_list[layer_idx]
-        G = self.num_kv_groups
+        full, stream = self._pools(layer_idx)
         out = torch.empty_like(query_states)
         scale = self.head_dim ** -0.5 if scale is None else scale
-        fk, fv = self.full_key_caches[layer_idx], self.full_value_caches[layer_idx]
-        sk, sv = self.streaming_key_caches[layer_idx], self.streaming_value_caches[layer_idx]
-        full = _hip.make_int4_pool(fk.quantized_data, fk.scale_zero, fv.quantized_data, fv.scale_zero, n, 0) if nf else None
-        stream = _hip.make_int4_pool(sk.quantized_data, sk.scale_zero, sv.quantized_data, sv.scale_zero, m, nf * G) if ns else None
-        _hip.attn_decode_int4_batched(query_states[:, 0], out[:, 0], G, full, stream, scale,
+        _hip.attn_decode_int4_batched(query_states[:, 0], out[:, 0], self.num_kv_groups, full, stream, scale,
                                       fused=(2 + int(self.fused_dequant)) if self.folded_decode else self.fused_dequant)
         return out

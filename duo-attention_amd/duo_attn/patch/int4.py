@@ -26,6 +26,13 @@ from .flashinfer_utils import apply_rope_inplace
 from .static_kv_cache import enable_duo_attention_static_kv_cache
 
 
+# Longest step that DuoAttentionStaticINT4KVCache(multi_token_decode=True) sends to the packed-pool kernel instead of
+# get() + the fp16 prefill kernel.  The entry point itself takes up to 64; the rule is "the largest T at which the new route is
+# faster at 128 K and at 1 M rows by more than the run-to-run spread".  NOT MEASURED YET: 16 is the largest power of two at which
+# the new route moves less than half the parent route's bytes per pool row at group 4 (profiles/int4_multi_token.md).
+MULTI_TOKEN_LIMIT = 16
+
+
 def duo_attention_forward_int4_kv(
     self,
     hidden_states: torch.Tensor,
@@ -57,6 +64,8 @@ def duo_attention_forward_int4_kv(
     kv_cache.put(layer_idx, key_states, value_states, dequantize=False)             # :225-230
     if q_len == 1 and past > 0:
         attn_output = kv_cache.decode_attention(layer_idx, query_states)            # :240-274 on the packed pools
+    elif kv_cache.multi_token_decode and past > 0 and 1 < q_len <= MULTI_TOKEN_LIMIT and groups <= 16:
+        attn_output = kv_cache.multi_token_attention(layer_idx, query_states)       # :239-274 on the packed pools (opt-in)
     else:
         attn_output = kv_cache.prefill_attention(layer_idx, query_states, key_states, value_states)   # :232-274
     kv_cache.compress(layer_idx)                                                    # :278

@@ -55,6 +55,8 @@
  *   duo_attn_prefill_workspace_bytes() doubled (2048 partials).  Results of a launch may be split — summed — differently than by a v5 build; outputs stay inside the same bar.
  * ABI version 7 (additions only, no signature changed): + duo_lambda_attn_fwd_bf16, duo_lambda_attn_bwd_bf16,
  *   duo_lambda_attn_bwd_workspace_bytes — the Λ-mask (streaming) attention of retrieval-head training, with its backward.
+ * ABI version 8 (additions only, no signature changed): + duo_attn_decode_int4_multi_f16, duo_attn_decode_int4_multi_batched_f16
+ *   — a step of 2..64 query tokens against non-empty INT4 pools, computed on the packed pools.
  *
  * Attention semantics (flash-attn 2.6.3 flash_attn_func, causal=True,
  * bottom-right aligned): a query at row i of the S new rows sees every key of
@@ -71,7 +73,7 @@
 extern "C" {
 #endif
 
-#define DUO_ABI_VERSION 7
+#define DUO_ABI_VERSION 8
 
 /* argument errors (negative so they never collide with hipError_t) */
 #define DUO_EINVAL   (-1)  /* bad pointer / size / stride                     */
@@ -466,6 +468,30 @@ int duo_attn_decode_int4_batched_f16(const void *q, int64_t q_batch_stride, int6
                                      const duo_int4_pool *full, const duo_int4_pool *stream_cls, float scale,
                                      int32_t head_dim, int32_t fused, void *workspace, int64_t workspace_bytes,
                                      void *stream);
+
+/* A step of n_tokens (1..64) fp16 query tokens against NON-EMPTY pools, straight over the packed rows (ABI v8): the later-chunk
+ * branch of demo/w8a8kv4_llama.py:239-274 — cache.get() dequantises both whole pools to fp16 scratch (demo/int4_kv.py:373-436)
+ * and flash_attn_func(causal=True) reads the scratch — without the scratch.  Called after the step's rows were quantised
+ * into the pools (both `len`s include them, so each must be >= n_tokens, else DUO_EINVAL): token i of a q head attends to
+ * rows [0, len - n_tokens + i] of its class's pool (bottom-right causal), over exactly the values duo_int4_dequantize_f16
+ * would have written in the form `fused & 1` (2 / 3 run as 0 / 1: there is no folded multi-token form).  q / out
+ * [n_tokens, n_q_heads, 128] fp16, strides in elements (q: multiples of 8, out: of 4).  16 / group tokens share one pass over
+ * the pool — the q columns the single-token kernel pads with zeros; more tokens take ceil(n_tokens / (16 / group)) passes, as a
+ * grid dimension.  group > 16: DUO_EGROUP.  Workspace: duo_attn_decode_workspace_bytes(n_tokens * n_q_heads, splits) for one
+ * batch row.  n_tokens == 1 is duo_attn_decode_int4_f16.                                                                  */
+int duo_attn_decode_int4_multi_f16(const void *q, int64_t q_token_stride, int64_t q_head_stride, void *out,
+                                   int64_t out_token_stride, int64_t out_head_stride, int32_t n_tokens, int32_t group,
+                                   const duo_int4_pool *full, const duo_int4_pool *stream_cls, float scale, int32_t head_dim,
+                                   int32_t fused, void *workspace, int64_t workspace_bytes, void *stream);
+/* the same for every batch row in one launch (demo/w8a8kv4_llama.py:239-274 with bsz > 1): q / out [B, n_tokens, n_q_heads, 128],
+ * the pools' batch rows duo_int4_pool::batch_stride_rows apart; n_batch * n_tokens <= 65535.  The un-batched form above is
+ * its n_batch = 1 case.                                                                                                    */
+int duo_attn_decode_int4_multi_batched_f16(const void *q, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                                           void *out, int64_t out_batch_stride, int64_t out_token_stride,
+                                           int64_t out_head_stride, int32_t n_batch, int32_t n_tokens, int32_t group,
+                                           const duo_int4_pool *full, const duo_int4_pool *stream_cls, float scale,
+                                           int32_t head_dim, int32_t fused, void *workspace, int64_t workspace_bytes,
+                                           void *stream);
 
 /* ---- RMSNorm: y = x * rsqrt(mean(x^2) + eps) * w, rows of `hidden` bf16 ---- */
 int duo_rmsnorm_bf16(const void *x, const void *w, void *y, int64_t n_rows,

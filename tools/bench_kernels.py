@@ -3,6 +3,8 @@
 
     python tools/bench_kernels.py prefill --nf 4 --past 65536 --chunk 16384 --reps 5
     python tools/bench_kernels.py decode  --ctx 131072 --reps 20        # all 32 layers of the bench pattern
+    python tools/bench_kernels.py decode_int4 --ctx 1048576 --q-len 2 4 16   # one layer: a T-token step on the packed pools
+                                                                        # against get() + fp16 prefill and the 1-token decode
 Prints one JSON line per case: avg ms, algorithmic TFLOP/s or GB/s.
 """
 import argparse
@@ -40,6 +42,66 @@ def time_it(fn, reps, warm=2):
     return sum(ts) / len(ts), ts[0], ts[len(ts) // 2]
 
 
+def int4_multi_token(a, dev, g):
+    """One layer of the INT4 dual cache (--nf retrieval + 8 - nf streaming kv heads, group 4, sink 128 + recent 256) holding
+    --ctx rows, the step's T rows included.  Per T, alternating in this process after a warm-up of each:
+      single  decode_attention            the existing one-token launch (the yardstick for a one-pass step)
+      multi   multi_token_attention       the T-token step on the packed pools
+      parent  prefill_attention           get() (both pools dequantised to fp16 scratch) + the fp16 prefill launch
+    Prints one JSON line per T: median / min / max ms of each, the ratios of the medians, the fp16 scratch of `parent`."""
+    import types
+
+    from duo_attn.int4_kv import DuoAttentionStaticINT4KVCache
+
+    class Shape(torch.nn.Module):      # what the cache reads of a model: device / dtype of a parameter, the head counts
+        def __init__(self):
+            super().__init__()
+            self.p = torch.nn.Parameter(torch.zeros(1, device=dev, dtype=torch.float16))
+            self.config = types.SimpleNamespace(num_hidden_layers=1, num_attention_heads=HQ, num_key_value_heads=HKV,
+                                                head_dim=D, hidden_size=HQ * D)
+
+    N, sink, recent, t_max = a.ctx, 128, 256, max(a.q_len)
+    heads = [[1.0] * a.nf + [0.0] * (HKV - a.nf)]
+    kv = DuoAttentionStaticINT4KVCache(Shape(), heads, 1, N, sink, recent, t_max, multi_token_decode=True)
+    for c in (kv.full_key_caches[0], kv.full_value_caches[0], kv.streaming_key_caches[0], kv.streaming_value_caches[0]):
+        if c.quantized_data.numel():
+            c.quantized_data.random_(0, 256, generator=g)
+            c.scale_zero.copy_((torch.rand(c.scale_zero.shape, generator=g, device=dev) * 0.3 + 0.01).to(torch.float16))
+    kv.kv_seq_len_list[0] = N
+
+    def timed(fn):
+        x, y = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        x.record()
+        fn()
+        y.record()
+        return x, y
+
+    for T in a.q_len:
+        kv.streaming_kv_seq_len_list[0] = sink + recent + T       # the window was full, then the step's rows were put
+        q = torch.randn(1, T, HQ, D, generator=g, device=dev).to(torch.float16)
+        kn = torch.randn(1, T, HKV, D, generator=g, device=dev).to(torch.float16)
+        routes = {"single": lambda: kv.decode_attention(0, q[:, :1]),
+                  "multi": lambda: kv.multi_token_attention(0, q),
+                  "parent": lambda: kv.prefill_attention(0, q, kn, kn)}
+        for fn in routes.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        evs = {name: [] for name in routes}
+        for _ in range(max(a.reps, 5)):
+            for name, fn in routes.items():
+                evs[name].append(timed(fn))
+        torch.cuda.synchronize()
+        ms = {name: sorted(x.elapsed_time(y) for x, y in e) for name, e in evs.items()}
+        med = {name: t[len(t) // 2] for name, t in ms.items()}
+        print(json.dumps({"case": f"int4 step ctx={N} nf={a.nf} T={T}",
+                          **{f"{name}_ms": {"median": round(med[name], 4), "min": round(t[0], 4), "max": round(t[-1], 4)}
+                             for name, t in ms.items()},
+                          "multi_over_single": round(med["multi"] / med["single"], 3),
+                          "parent_over_multi": round(med["parent"] / med["multi"], 3),
+                          "parent_scratch_MB": round(sum(b.numel() for b in kv._scratch.values()) * 2 / 1e6, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["prefill", "decode", "decode_int4", "linear"])
@@ -51,6 +113,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--uniform-nf", type=int, default=-1, help="decode: every layer has this many retrieval kv heads")
+    ap.add_argument("--q-len", type=int, nargs="+", default=None,
+                    help="decode_int4: time a step of T tokens (one layer, --nf retrieval kv heads, --ctx rows) three ways")
     a = ap.parse_args()
     from duo_attn import _hip
     from duo_attn.backend import get_backend
@@ -113,6 +177,8 @@ def main():
         flops = 4 * D * G * (nf * (S * past + tri) + ns * (S * min(past, W) + tri))
         print(json.dumps({"case": f"prefill nf={nf} past={past} S={S}", "avg_ms": avg, "min_ms": mn,
                           "tflops_avg": flops / avg / 1e9, "tflops_best": flops / mn / 1e9}))
+    elif a.what == "decode_int4" and a.q_len:
+        int4_multi_token(a, dev, g)
     elif a.what == "decode_int4":
         import bench
 
