@@ -280,3 +280,131 @@ def _simulate_group_communicator(logs, plain_too=False):
                     progress = True
     stuck = {r: q[0] for r, q in enumerate(queues) if q}
     assert not stuck, f"the group communicator cannot make progress (head batch per rank): {stuck}"
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# dead rows and guard bytes (tests/test_dead_rows_gpu.py; DESIGN §4 "live rows only")
+# ----------------------------------------------------------------------------------------------------------------------
+GUARD16, GUARD8 = 0x5A5A, 0x5A          # the bit pattern of guard bytes (bf16 1.5e16, fp16 203.25: finite either way)
+DEAD_KINDS = ("nan", "huge")            # poison of 16-bit float buffers
+INT4_DEAD_KINDS = ("scale_nan", "scale_inf", "scale_max", "zero_nan", "zero_inf", "zero_max")
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    """same-size integer view (any strides): comparisons through it are bit comparisons, NaN == NaN included"""
+    return t if t.dtype == torch.uint8 else t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def dead_values(shape, dtype, kind: str, device, sz=False) -> torch.Tensor:
+    """what the bytes outside a live region are set to.  kind: "zero", "guard" (GUARD16 / GUARD8), "nan" (bf16 0x7FC0,
+    fp16 0x7E00), "huge" (bf16 +-3e38, fp16 +-65504, the sign alternating element by element), or — packed INT4 pools — one
+    of INT4_DEAD_KINDS: nibble bytes 0xFF, and in a scale-zero pool (``sz``: [..., 2] fp16) the named one of scale / zero
+    set to NaN, +Inf or 65504, the other to 1.0; 16-bit float buffers next to such pools get NaN / +-huge."""
+    if dtype == torch.uint8:
+        return torch.full(shape, {"zero": 0, "guard": GUARD8}.get(kind, 0xFF), dtype=torch.uint8, device=device)
+    if dtype == torch.float32:      # (fp32 outputs — the Λ forward's LSE — are only ever guarded)
+        assert kind == "guard", kind
+        return torch.full(shape, GUARD16 << 16 | GUARD16, dtype=torch.int32, device=device).view(dtype)
+    assert dtype in (torch.bfloat16, torch.float16), dtype
+    if kind == "zero":
+        return torch.zeros(shape, dtype=dtype, device=device)
+    if kind == "guard":
+        return torch.full(shape, GUARD16, dtype=torch.int16, device=device).view(dtype)
+    if kind in INT4_DEAD_KINDS:
+        which, what = kind.split("_")
+        if sz:
+            assert dtype == torch.float16 and shape[-1] == 2
+            bits = {"nan": 0x7E00, "inf": 0x7C00, "max": 0x7BFF}[what]
+            out = torch.full(shape, 0x3C00, dtype=torch.int16, device=device)       # 1.0
+            out[..., 0 if which == "scale" else 1] = bits
+            return out.view(dtype)
+        kind = "nan" if what == "nan" else "huge"
+    if kind == "nan":
+        return torch.full(shape, 0x7FC0 if dtype == torch.bfloat16 else 0x7E00, dtype=torch.int16, device=device).view(dtype)
+    assert kind == "huge", kind
+    big = 3e38 if dtype == torch.bfloat16 else 65504.0
+    n = 1
+    for s in shape:
+        n *= s
+    sign = 1.0 - 2.0 * (torch.arange(n, device=device) % 2).float()
+    return (sign * big).to(dtype).view(shape)
+
+
+class DeadBuf:
+    """A device buffer ``big`` with a live region inside it: ``view`` (any strided view of ``big``; for a pool its first
+    ``n_live`` rows).  ``reset(kind)`` restores the live bytes to what they were at construction and sets every other byte
+    to ``dead_values(kind)``; ``assert_dead(kind)`` checks that every byte outside the (possibly grown) live region still
+    holds exactly that — bit for bit."""
+
+    def __init__(self, big: torch.Tensor, view: torch.Tensor, n_live=None, sz=False):
+        self.big, self.view, self.sz = big, view, sz
+        self.live = view if n_live is None else view[..., :n_live, :, :]
+        self.initial = big.clone()
+        self.dead = self.dead_mask(self.live)
+
+    @classmethod
+    def guarded(cls, big: torch.Tensor, view: torch.Tensor) -> "DeadBuf":
+        """an OUTPUT region ``view`` of ``big``: ``reset("guard")`` sets every byte, the view's included, to the guard
+        pattern; ``assert_dead("guard")`` after the call checks the bytes outside the view"""
+        b = cls(big, view)
+        b.initial = b.values("guard")
+        return b
+
+    def dead_mask(self, live: torch.Tensor) -> torch.Tensor:
+        m = torch.ones(self.big.shape, dtype=torch.bool, device=self.big.device)
+        assert m.stride() == self.big.stride()
+        torch.as_strided(m, live.shape, live.stride(), live.storage_offset() - self.big.storage_offset()).fill_(False)
+        return m
+
+    def at_live(self, t: torch.Tensor, live: torch.Tensor = None) -> torch.Tensor:
+        """the live region of ``t``, a tensor laid out like ``big`` (``initial``, a clone, ...)"""
+        live = self.live if live is None else live
+        return torch.as_strided(t, live.shape, live.stride(), live.storage_offset() - self.big.storage_offset() + t.storage_offset())
+
+    def values(self, kind):
+        return dead_values(self.big.shape, self.big.dtype, kind, self.big.device, self.sz)
+
+    def reset(self, kind: str):
+        self.big.copy_(torch.where(self.dead, self.values(kind), self.initial))
+        return self
+
+    def assert_dead(self, kind: str, live: torch.Tensor = None, what=""):
+        m = self.dead if live is None else self.dead_mask(live)
+        got, want = _bits(self.big)[m], _bits(self.values(kind))[m]
+        bad = got != want
+        assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the declared region changed ({kind})"
+
+
+def dead_embed(live: torch.Tensor, cap=None, lead=0, tail=130, gap=4, head_major=False, device="cuda:0", sz=False) -> DeadBuf:
+    """live [..., T, h, X] (CPU) -> a DeadBuf whose ``view`` is [..., cap, h, X] (cap >= T rows; default T) inside a
+    larger buffer: ``lead`` rows before and ``tail`` rows after the cap rows, ``gap`` heads before and after the h heads;
+    token-major ([rows, heads, X]) or head-major ([heads, rows, X], viewed [rows, heads, X]).  A leading batch dimension
+    gets the same slack inside every batch row.  view[..., :T] = live."""
+    *b, T, h, X = live.shape
+    cap = T if cap is None else cap
+    assert cap >= T
+    rows, heads = lead + cap + tail, h + 2 * gap
+    if head_major:
+        big = torch.zeros(*b, heads, rows, X, dtype=live.dtype, device=device)
+        view = big[..., gap:gap + h, lead:lead + cap, :].transpose(-3, -2)
+    else:
+        big = torch.zeros(*b, rows, heads, X, dtype=live.dtype, device=device)
+        view = big[..., lead:lead + cap, gap:gap + h, :]
+    view[..., :T, :, :].copy_(live)
+    return DeadBuf(big, view, n_live=T, sz=sz)
+
+
+def guard_embed(shape, dtype, lead=130, tail=130, gap=4, device="cuda:0") -> DeadBuf:
+    """an OUTPUT of ``shape`` [..., T, h, X] as a view into a larger buffer (at least ``lead`` / ``tail`` rows around it,
+    ``gap`` heads either side): ``reset("guard")`` before a call, ``assert_dead("guard")`` after it"""
+    buf = dead_embed(torch.zeros(shape, dtype=dtype), lead=lead, tail=tail, gap=gap, device=device)
+    return DeadBuf.guarded(buf.big, buf.view)
+
+
+def guard_flat(shape, dtype, pad_elems, device="cuda:0") -> DeadBuf:
+    """a CONTIGUOUS output of ``shape`` (an ABI that takes a bare pointer) with ``pad_elems`` guard elements before and after"""
+    n = 1
+    for s in shape:
+        n *= s
+    big = torch.zeros(n + 2 * pad_elems, dtype=dtype, device=device)
+    return DeadBuf.guarded(big, big[pad_elems:pad_elems + n].view(shape))

@@ -137,7 +137,7 @@ def test_stream_compress(sink, recent, cur, n_new, head_major):
     assert n == en
     assert torch.equal(kp.cpu()[:n], ek[:n]) and torch.equal(vp.cpu()[:n], ev[:n])
     # rows past the live length are untouched
-    assert torch.equal(kp.cpu()[n:], pool_k[n:])
+    assert torch.equal(kp.cpu()[n:], pool_k[n:]) and torch.equal(vp.cpu()[n:], pool_v[n:])
 
 
 # ----------------------------------------------------------------------------- RMSNorm
