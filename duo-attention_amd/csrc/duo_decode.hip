@@ -317,219 +317,9 @@ __device__ unsigned long long duo_decode_timing[2048][12];
 #define DUO_DRT(k) do { } while (0)
 #endif
 
-// grid.x = (kv head, split) pairs of the full class then of the streaming class
-// grid.y = group / GT
-
-template <int GT, bool NT, bool PREFETCH, bool FUSED>
-__global__ __launch_bounds__(256) void duo_decode_split_kernel(const DecodeParams P, const CompressParams CP) {
-    DUO_DT(0);
-    DUO_DRT(8);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: scalar loop control
-    const int sub = lane & 15;   // which 8-dim slice of the 128-dim row
-    const int tg = lane >> 4;    // which of the 4 rows a wave-load covers
-
-    int b = blockIdx.x;
-    const int ci = b < P.nblk_full ? 0 : 1;
-    if (ci) b -= P.nblk_full;
-    DuoClassDev C = duo_select(P.cls[0], P.cls[1], ci != 0);
-    const int bz = blockIdx.z;      // batch row
-    duo_class_batch_row(C, bz);
-    bf16_t *const out_row = P.out + (int64_t)bz * P.out_bs;
-    float *const ws_ml_row = P.ws_ml + (int64_t)bz * P.ws_row_floats, *const ws_acc_row = P.ws_acc + (int64_t)bz * P.ws_row_floats;
-    int app_row = P.app_row;
-    float pos = P.pos;
-    if constexpr (FUSED) {
-        if (P.dev_state) {   // uniform scalar loads
-            app_row = P.dev_state[0];
-            C.a.len = ci ? P.dev_state[1] : app_row;
-            pos = (float)P.dev_state[2] + P.pos_delta;
-        }
-    }
-    const int splits = ci ? P.splits[1] : P.splits[0];
-    const int kvh = b / splits;
-    const int split = b - kvh * splits;
-    const int qh0 = C.q_head_offset + kvh * P.group + blockIdx.y * GT;
-
-    // balanced static partition: the head's ceil(L/64) 64-token units are dealt to the splits as
-    // evenly as possible, so every workgroup of the (single-round) grid streams the same bytes
-    // FUSED: the scan covers the cached rows only; the new token is handled after the loop
-    const int L = FUSED ? C.a.len : C.a.len + C.b.len;
-    const int units = (L + 63) >> 6;
-    const int uq = units / splits, ur = units - uq * splits;
-    const int u0 = split * uq + min(split, ur);
-    const int un = uq + (split < ur ? 1 : 0);
-    const int c0 = u0 << 6;
-    const int c1 = min((u0 + un) << 6, L);
-    const int per_wave = (((c1 - c0 + 3) >> 2) + 15) & ~15;  // quarter of the chunk, multiple of 16
-    const int w0 = __builtin_amdgcn_readfirstlane(c0 + wave * per_wave);
-    const int w1 = __builtin_amdgcn_readfirstlane(min(w0 + per_wave, c1));
-
-    RowSrc src;
-    src.ka = C.a.k + kvh * C.a.head_stride + sub * 8;
-    src.va = C.a.v + kvh * C.a.head_stride + sub * 8;
-    src.kb = C.b.k + kvh * C.b.head_stride + sub * 8;
-    src.vb = C.b.v + kvh * C.b.head_stride + sub * 8;
-    src.tsa = C.a.token_stride;
-    src.tsb = C.b.token_stride;
-    src.lenA = C.a.len;
-    DUO_DT(4);
-
-    // RoPE factors of this lane's 8 dims (FUSED): dims 8*sub+e pair with dims (8*sub+e) ^ 64, i.e.
-    // with the slice of lane sub ^ 8; both slices of a pair use frequency index (8*sub+e) & 63
-    float cs[8], sn[8];
-    if constexpr (FUSED) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sincos_rev(pos * P.inv_freq[((sub & 7) << 3) + e], sn[e], cs[e]);
-    }
-    DUO_DT(5);
-    // x: own slice, y: partner slice -> rotated own slice (first half: x*c - y*s, second half: x*c + y*s)
-    auto rope8 = [&](const u32x4 &own, const u32x4 &partner, float (&o)[8]) {
-        float x[8], y[8];
-        unpack8(own, x);
-        unpack8(partner, y);
-        const float sgn = sub < 8 ? -1.f : 1.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            // round to bf16 exactly like the standalone RoPE kernel does before the attention reads it
-            o[e] = __uint_as_float(f32_to_bf16_bits(x[e] * cs[e] + sgn * y[e] * sn[e]) << 16);
-        }
-    };
-
-    float qf[GT][8];
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        const bf16_t *qrow = P.q + (int64_t)bz * P.q_bs + (int64_t)(qh0 + g) * P.q_head_stride;
-        const u32x4 w = *reinterpret_cast<const u32x4 *>(qrow + sub * 8);
-        if constexpr (FUSED) {
-            const u32x4 wp = *reinterpret_cast<const u32x4 *>(qrow + (sub ^ 8) * 8);
-            rope8(w, wp, qf[g]);
-        } else {
-            unpack8(w, qf[g]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[g][e] *= P.scale_log2e;
-    }
-
-    float m[GT], l[GT], acc[GT][8];
-    DUO_DT(1);
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        m[g] = kNegSentinel;
-        l[g] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
-    }
-
-    // Main loop: the 16-token groups that lie wholly in segment A and inside the wave's range.  Their
-    // addresses are a uniform base (SGPR pair, advanced per group) + four per-lane 32-bit byte offsets that
-    // never change: no per-load address arithmetic, and straight-line code with a FIXED number of loads
-    // in flight at every use — with a conditional prefetch hipcc has to wait with the smaller count, which
-    // on the common path means waiting for the loads it has just issued.  The prefetch of the group after
-    // the last one re-reads the last one (never consumed).  What is left — a partial group, segment B
-    // rows — goes through the general clamped loader, one group at a time.
-    const char *kA = reinterpret_cast<const char *>(C.a.k + kvh * C.a.head_stride);
-    const char *vA = reinterpret_cast<const char *>(C.a.v + kvh * C.a.head_stride);
-    uint32_t roff[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) roff[u] = (uint32_t)(((4 * u + tg) * src.tsa + sub * 8) * 2);
-    auto load_fast = [&](int t, u32x4 (&kb)[4], u32x4 (&vb)[4]) __attribute__((always_inline)) {
-        // (readfirstlane: keeps the group base in SGPRs — loop strength reduction otherwise turns it into
-        // a per-lane 64-bit pointer whose registers then collide with loads still in flight)
-        gchar_t *kt = uniform_gptr(kA + (int64_t)t * src.tsa * 2), *vt = uniform_gptr(vA + (int64_t)t * src.tsa * 2);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            // (empty asm: the 32-bit offset is re-materialised as such in THIS basic block, so instruction
-            // selection sees sgpr base + zext(vgpr32) and emits the saddr form; hoisted out of the loop the
-            // zero-extension becomes a 64-bit VGPR pair and every load pays a v_lshl_add_u64)
-            // (in place, no copy: a temporary would be a fresh register — possibly one a load still in
-            // flight is about to write, which costs a vmcnt(0))
-            asm volatile("" : "+v"(roff[u]));
-            kb[u] = ld16g<NT>(kt + roff[u]);
-            vb[u] = ld16g<NT>(vt + roff[u]);
-        }
-    };
-
-    int t_rest = w0;
-    if constexpr (PREFETCH) {
-        const int fast_end = min(w1, C.a.len);
-        const int nfast = fast_end > w0 ? (fast_end - w0) / kTokPerIter : 0;
-        if (nfast > 0) {
-            const int t_last = w0 + (nfast - 1) * kTokPerIter;
-            u32x4 k0[4], v0[4], k1[4], v1[4];
-            load_fast(w0, k0, v0);
-            // (sched_barrier: the loads stay ahead of the arithmetic on the other buffer — the scheduler
-            // would otherwise sink them next to their first use, one iteration later.)
-            for (int t = w0;; t += 2 * kTokPerIter) {
-                load_fast(min(t + kTokPerIter, t_last), k1, v1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (P.dbg & 64u) l[0] += __uint_as_float((k0[0].x ^ k0[1].y ^ k0[2].z ^ k0[3].w ^ v0[0].x ^ v0[1].y ^ v0[2].z ^ v0[3].w) & 1u);
-                else consume_rows<GT, true>(k0, v0, t, tg, w1, qf, m, l, acc);
-                if (t >= t_last) break;
-                load_fast(min(t + 2 * kTokPerIter, t_last), k0, v0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (P.dbg & 64u) l[0] += __uint_as_float((k1[0].x ^ k1[1].y ^ k1[2].z ^ k1[3].w ^ v1[0].x ^ v1[1].y ^ v1[2].z ^ v1[3].w) & 1u);
-                else consume_rows<GT, true>(k1, v1, t + kTokPerIter, tg, w1, qf, m, l, acc);
-                if (t + kTokPerIter >= t_last) break;
-            }
-            t_rest = w0 + nfast * kTokPerIter;
-        }
-    }
-    {
-        u32x4 k0[4], v0[4];
-        for (int t = t_rest; t < w1; t += kTokPerIter) {
-            load_rows<NT>(src, t, tg, w1, k0, v0);
-            consume_rows<GT>(k0, v0, t, tg, w1, qf, m, l, acc);
-        }
-    }
-
-    DUO_DT(2);
-    if constexpr (FUSED) {
-        // ---- the new token: last split of the kv head, wave 0, token group 0 (one 16-lane DPP row) ----
-        if (split == splits - 1 && wave == 0 && tg == 0) {
-            const bf16_t *krow = C.b.k + (int64_t)kvh * C.b.head_stride;
-            const bf16_t *vrow = C.b.v + (int64_t)kvh * C.b.head_stride;
-            const u32x4 kw = *reinterpret_cast<const u32x4 *>(krow + sub * 8);
-            const u32x4 kp = *reinterpret_cast<const u32x4 *>(krow + (sub ^ 8) * 8);
-            const u32x4 vw = *reinterpret_cast<const u32x4 *>(vrow + sub * 8);
-            float kf[8], vf[8];
-            rope8(kw, kp, kf);
-            unpack8(vw, vf);
-            u32x4 kr;   // rotated slice, bf16
-            kr.x = (__float_as_uint(kf[0]) >> 16) | (__float_as_uint(kf[1]) & 0xffff0000u);
-            kr.y = (__float_as_uint(kf[2]) >> 16) | (__float_as_uint(kf[3]) & 0xffff0000u);
-            kr.z = (__float_as_uint(kf[4]) >> 16) | (__float_as_uint(kf[5]) & 0xffff0000u);
-            kr.w = (__float_as_uint(kf[6]) >> 16) | (__float_as_uint(kf[7]) & 0xffff0000u);
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-                float d = qf[g][0] * kf[0];
-#pragma unroll
-                for (int e = 1; e < 8; ++e) d = fmaf(qf[g][e], kf[e], d);
-                const float sc_ = row16_allreduce_sum(d);
-                const float mn = fmaxf(m[g], sc_);
-                const float alpha = fast_exp2(m[g] - mn);
-                const float p_ = fast_exp2(sc_ - mn);
-                l[g] = fmaf(l[g], alpha, p_);
-                m[g] = mn;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[g][e] = fmaf(p_, vf[e], acc[g][e] * alpha);
-            }
-            // retrieval heads: the rotated key and the value join the pool (row app_row is outside
-            // every scan range of this launch)
-            if (ci == 0 && blockIdx.y == 0) {
-                const int64_t po = (int64_t)bz * P.app_bs + (int64_t)app_row * P.app_ts + (int64_t)kvh * P.app_hs + sub * 8;
-                *reinterpret_cast<u32x4 *>(P.app_k + po) = kr;
-                *reinterpret_cast<u32x4 *>(P.app_v + po) = vw;
-            }
-        }
-    }
-
-#include "duo_decode_tail.inc"
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// duo_decode_scan_kernel — the same split-KV scan behind a SHORT prologue (round 3; duo_decode_split_kernel above is
-// kept as the general fallback and as the same-box A/B, debug bit 9).
+// duo_decode_scan_kernel — the split-KV scan of every decode launch, behind a SHORT prologue.
+// grid.x = (kv head, split) pairs of the full class then of the streaming class; grid.y = group / GT; grid.z = batch row.
 //
 // What the anatomy of the launch showed (profiles/r2_decode_wgs.md): all 256 workgroups run their prologue at the
 // same time, so HBM idles for its whole length, and the prologue was a chain of DEPENDENT memory round trips of
@@ -547,6 +337,10 @@ __global__ __launch_bounds__(256) void duo_decode_split_kernel(const DecodeParam
 //   * the new token's k/v rows sit in registers through the scan, so the epilogue of the last split has no load.
 // pack0 = splits of the retrieval class (bits 0-11) | q heads per kv head (12-17) | first q head of the class (18-31);
 // pack1 = q head stride in elements (0-15) | rows of the retrieval class's segment B (16-31).
+//
+// WIDE: the form for a launch whose fields do not fit those packed widths (decode_scan_eligible; debug bit 9 takes it
+// for every launch).  The ten leading arguments are ignored and BOTH classes are described by P at full width, picked
+// field by field; everything behind the class set-up is the same source.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(2))) __bf16 hw_bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
@@ -556,7 +350,7 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16_rne(float lo, float hi) {
     return *reinterpret_cast<uint32_t *>(&r);
 }
 
-template <int GT, bool NT, bool FUSED>
+template <int GT, bool NT, bool FUSED, bool WIDE>
 __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__restrict__ q, const bf16_t *k0,
                                                               const bf16_t *v0, const int32_t *dev_state, int32_t len0,
                                                               uint32_t pack0, int32_t nblk_full, uint32_t hs0,
@@ -569,10 +363,16 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
     const int sub = lane & 15;   // which 8-dim slice of the 128-dim row
     const int tg = lane >> 4;    // which of the 4 rows a wave-load covers
 
-    // ---- class description: retrieval class from the preloaded SGPRs, streaming class from the kernarg segment -----
+    // ---- class description.  Packed form: retrieval class from the leading scalar arguments, streaming class from the
+    //      kernarg segment.  Wide form: both classes from the kernarg segment -----------------------------------------
+    if constexpr (WIDE) {
+        q = P.q;
+        dev_state = P.dev_state;
+        nblk_full = P.nblk_full;
+    }
     int b = blockIdx.x;
     const int ci = b < nblk_full ? 0 : 1;
-    const int group = (int)((pack0 >> 12) & 63u);
+    const int group = WIDE ? P.group : (int)((pack0 >> 12) & 63u);
     const bf16_t *ak = k0, *av = v0;
     int64_t a_ts = ts0, a_hs = hs0;
     int a_len = len0, b_len = (int)(pack1 >> 16), splits = (int)(pack0 & 4095u), qoff = (int)(pack0 >> 18);
@@ -588,7 +388,18 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
             have_state = true;
         }
     }
-    if (ci) {
+    if constexpr (WIDE) {
+        if (ci) b -= nblk_full;
+        const DuoSegDev A = duo_select(P.cls[0].a, P.cls[1].a, ci != 0);
+        ak = A.k;
+        av = A.v;
+        a_ts = A.token_stride;
+        a_hs = A.head_stride;
+        a_len = A.len;
+        b_len = ci ? P.cls[1].b.len : P.cls[0].b.len;
+        splits = ci ? P.splits[1] : P.splits[0];
+        qoff = ci ? P.cls[1].q_head_offset : P.cls[0].q_head_offset;
+    } else if (ci) {
         asm volatile("" ::: "memory");   // a real branch: retrieval workgroups must not wait for these scalar loads
         b -= nblk_full;
         ak = P.cls[1].a.k;
@@ -616,7 +427,9 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
     const int split = b - kvh * splits;
     const int qh0 = qoff + kvh * group + blockIdx.y * GT;
 
-    // balanced static partition (as duo_decode_split_kernel): the head's 64-token units dealt evenly to the splits
+    // balanced static partition: the head's ceil(L/64) 64-token units are dealt to the splits as evenly as possible, so
+    // every workgroup of the (single-round) grid streams the same bytes.  FUSED: the scan covers the cached rows only;
+    // the new token is handled after the loop
     const int L = FUSED ? a_len : a_len + b_len;
     const int units = (L + 63) >> 6;
     int u0, u1;
@@ -658,7 +471,7 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
         fr1 = *reinterpret_cast<const f32x4 *>(fp + 4);
     }
     // (b) q rows (own slice, and the rotation partner's when q arrives un-rotated)
-    const uint32_t qhs = pack1 & 0xffffu;
+    const int64_t qhs = WIDE ? P.q_head_stride : (int64_t)(pack1 & 0xffffu);
     u32x4 qw[GT], qp[GT];
 #pragma unroll
     for (int g = 0; g < GT; ++g) {
@@ -758,12 +571,24 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
         for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
     }
 
-    // ---- main loop: as duo_decode_split_kernel (uniform SGPR base + constant per-lane offsets, a fixed number of
-    //      loads in flight at every use); its first group is already on the way -------------------------------------
+    // ---- main loop: the 16-token groups that lie wholly in segment A and inside the wave's range; the first one is
+    //      already on the way.  Their addresses are a uniform base (SGPR pair, advanced per group) + four per-lane
+    //      32-bit byte offsets that never change: no per-load address arithmetic, and straight-line code with a FIXED
+    //      number of loads in flight at every use — with a conditional prefetch hipcc has to wait with the smaller
+    //      count, which on the common path means waiting for the loads it has just issued.  The prefetch of the group
+    //      after the last one re-reads the last one (never consumed).  What is left — a partial group, segment B rows
+    //      — goes through the general clamped loader, one group at a time. ------------------------------------------
     auto load_fast = [&](int t, u32x4 (&kb)[4], u32x4 (&vb)[4]) __attribute__((always_inline)) {
+        // (readfirstlane: keeps the group base in SGPRs — loop strength reduction otherwise turns it into
+        // a per-lane 64-bit pointer whose registers then collide with loads still in flight)
         gchar_t *kt = uniform_gptr(kA + (int64_t)t * a_ts * 2), *vt = uniform_gptr(vA + (int64_t)t * a_ts * 2);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
+            // (empty asm: the 32-bit offset is re-materialised as such in THIS basic block, so instruction
+            // selection sees sgpr base + zext(vgpr32) and emits the saddr form; hoisted out of the loop the
+            // zero-extension becomes a 64-bit VGPR pair and every load pays a v_lshl_add_u64)
+            // (in place, no copy: a temporary would be a fresh register — possibly one a load still in
+            // flight is about to write, which costs a vmcnt(0))
             asm volatile("" : "+v"(roff[u]));
             kb[u] = ld16g<NT>(kt + roff[u]);
             vb[u] = ld16g<NT>(vt + roff[u]);
@@ -772,6 +597,8 @@ __global__ __launch_bounds__(256) void duo_decode_scan_kernel(const bf16_t *__re
     int t_rest = w0;
     if (nfast > 0) {
         const int t_last = w0 + (nfast - 1) * kTokPerIter;
+        // (sched_barrier: the loads stay ahead of the arithmetic on the other buffer — the scheduler would otherwise
+        // sink them next to their first use, one iteration later.)
         for (int t = w0;; t += 2 * kTokPerIter) {
             load_fast(min(t + kTokPerIter, t_last), k1r, v1r);      // (behind the last group: re-reads it, never consumed)
             __builtin_amdgcn_sched_barrier(0);
@@ -854,7 +681,7 @@ extern "C" int64_t duo_attn_decode_workspace_bytes(int32_t n_q_heads, int32_t ma
 }
 
 static int decode_target_wgs() {
-    // workgroups the split kernel aims for across both classes (tuning knob, read once)
+    // workgroups the scan kernel aims for across both classes (tuning knob, read once)
     static int v = [] {
         const char *e = getenv("DUO_DECODE_TARGET_WGS");
         const int x = e ? atoi(e) : 0;
@@ -990,7 +817,7 @@ static int decode_plan(const void *q, int64_t q_head_stride, void *out, int64_t 
     return 0;
 }
 
-// The short-prologue scan kernel takes the retrieval class's addressing in 14 preloaded dwords; it applies when those
+// The packed form of the scan kernel takes the retrieval class's addressing in 14 leading dwords; it applies when those
 // fields fit their packed widths (always, for the pools and activations this library's callers hand over).
 static bool decode_scan_eligible(const DecodeParams &P) {
     const DuoClassDev &F = P.cls[0];
@@ -1006,47 +833,44 @@ static bool decode_scan_eligible(const DecodeParams &P) {
 }
 
 template <bool FUSED>
-static int decode_launch_split(const DecodePlan &D, const CompressParams &CP, hipStream_t st) {
+static int decode_launch_scan(const DecodePlan &D, const CompressParams &CP, hipStream_t st) {
     if (D.nblk <= 0) return 0;
     const DecodeParams &P = D.P;
     dim3 grid(D.nblk, P.group / D.gt, D.n_batch), block(256);
     const uint32_t fl = duo_get_debug_flags();
     const bool nt = !(fl & 4u);        // debug bit 2: plain (temporal) K/V loads
-    const bool pf = !(fl & 8u);        // debug bit 3: no register prefetch of the next 16 tokens
-    // debug bit 9: stay on duo_decode_split_kernel (the long-prologue form: same-box A/B of the two scans)
-    if (pf && !(fl & 512u) && decode_scan_eligible(P)) {
-        const DuoClassDev &F = P.cls[0];
-        const bool hasF = F.n_kv_heads > 0;
-        const uint32_t pack0 = hasF ? ((uint32_t)P.splits[0] | ((uint32_t)P.group << 12) | ((uint32_t)F.q_head_offset << 18))
-                                    : (1u | ((uint32_t)P.group << 12));
-        const uint32_t pack1 = (uint32_t)P.q_head_stride | (hasF ? (uint32_t)F.b.len << 16 : 0u);
-        const uint32_t hs0 = hasF ? (uint32_t)F.a.head_stride : 0u, ts0 = hasF ? (uint32_t)F.a.token_stride : 0u;
-        const int32_t len0 = hasF ? F.a.len : 0;
-#define DUO_LAUNCH_SCAN(GT_)                                                                                          \
-    do {                                                                                                              \
-        if (nt) hipLaunchKernelGGL((duo_decode_scan_kernel<GT_, true, FUSED>), grid, block, 0, st, P.q, F.a.k, F.a.v,     \
-                                   P.dev_state, len0, pack0, P.nblk_full, hs0, ts0, pack1, P, CP);                       \
-        else hipLaunchKernelGGL((duo_decode_scan_kernel<GT_, false, FUSED>), grid, block, 0, st, P.q, F.a.k, F.a.v,       \
-                                P.dev_state, len0, pack0, P.nblk_full, hs0, ts0, pack1, P, CP);                          \
-    } while (0)
-        if (D.gt == 4) DUO_LAUNCH_SCAN(4);
-        else if (D.gt == 2) DUO_LAUNCH_SCAN(2);
-        else DUO_LAUNCH_SCAN(1);
-#undef DUO_LAUNCH_SCAN
-        DUO_HIP_CHECK_LAUNCH();
-        return 0;
+    // debug bit 9: the wide form for every launch (otherwise only for fields that do not fit the packed arguments)
+    const bool wide = (fl & 512u) || !decode_scan_eligible(P);
+    const DuoClassDev &F = P.cls[0];
+    const bool hasF = F.n_kv_heads > 0;
+    // the packed arguments (the wide form ignores them)
+    uint32_t pack0 = 0, pack1 = 0, hs0 = 0, ts0 = 0;
+    int32_t len0 = 0;
+    if (!wide) {
+        pack0 = hasF ? ((uint32_t)P.splits[0] | ((uint32_t)P.group << 12) | ((uint32_t)F.q_head_offset << 18))
+                     : (1u | ((uint32_t)P.group << 12));
+        pack1 = (uint32_t)P.q_head_stride | (hasF ? (uint32_t)F.b.len << 16 : 0u);
+        if (hasF) {
+            hs0 = (uint32_t)F.a.head_stride;
+            ts0 = (uint32_t)F.a.token_stride;
+            len0 = F.a.len;
+        }
     }
-#define DUO_LAUNCH_DECODE(GT_)                                                                                      \
-    do {                                                                                                            \
-        if (nt && pf) hipLaunchKernelGGL((duo_decode_split_kernel<GT_, true, true, FUSED>), grid, block, 0, st, P, CP);   \
-        else if (nt) hipLaunchKernelGGL((duo_decode_split_kernel<GT_, true, false, FUSED>), grid, block, 0, st, P, CP);   \
-        else if (pf) hipLaunchKernelGGL((duo_decode_split_kernel<GT_, false, true, FUSED>), grid, block, 0, st, P, CP);   \
-        else hipLaunchKernelGGL((duo_decode_split_kernel<GT_, false, false, FUSED>), grid, block, 0, st, P, CP);          \
+#define DUO_LAUNCH_SCAN(GT_, NT_, WIDE_)                                                                               \
+    hipLaunchKernelGGL((duo_decode_scan_kernel<GT_, NT_, FUSED, WIDE_>), grid, block, 0, st, P.q, F.a.k, F.a.v,          \
+                       P.dev_state, len0, pack0, P.nblk_full, hs0, ts0, pack1, P, CP)
+#define DUO_LAUNCH_SCAN_GT(GT_)                                                                                        \
+    do {                                                                                                               \
+        if (nt && !wide) DUO_LAUNCH_SCAN(GT_, true, false);                                                            \
+        else if (nt) DUO_LAUNCH_SCAN(GT_, true, true);                                                                 \
+        else if (!wide) DUO_LAUNCH_SCAN(GT_, false, false);                                                            \
+        else DUO_LAUNCH_SCAN(GT_, false, true);                                                                        \
     } while (0)
-    if (D.gt == 4) DUO_LAUNCH_DECODE(4);
-    else if (D.gt == 2) DUO_LAUNCH_DECODE(2);
-    else DUO_LAUNCH_DECODE(1);
-#undef DUO_LAUNCH_DECODE
+    if (D.gt == 4) DUO_LAUNCH_SCAN_GT(4);
+    else if (D.gt == 2) DUO_LAUNCH_SCAN_GT(2);
+    else DUO_LAUNCH_SCAN_GT(1);
+#undef DUO_LAUNCH_SCAN_GT
+#undef DUO_LAUNCH_SCAN
     DUO_HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -1054,7 +878,25 @@ static int decode_launch_split(const DecodePlan &D, const CompressParams &CP, hi
 static int attn_decode_impl(const void *q, int64_t q_batch_stride, int64_t q_head_stride, void *out,
                             int64_t out_batch_stride, int64_t out_head_stride, int32_t n_batch, int32_t group,
                             const duo_head_class *full, const duo_head_class *stream_cls, float scale, int32_t head_dim,
-                            void *workspace, int64_t workspace_bytes, void *stream);
+                            void *workspace, int64_t workspace_bytes, void *stream) {
+    if (head_dim != DUO_HEAD_DIM) return DUO_EHEADDIM;
+    if (q == nullptr || out == nullptr || group <= 0) return DUO_EINVAL;
+    DecodePlan D;
+    int rc = decode_plan(q, q_head_stride, out, out_head_stride, group, full, stream_cls, scale, workspace,
+                         workspace_bytes, D, n_batch, q_batch_stride, out_batch_stride);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = decode_launch_scan<false>(D, CompressParams{}, st);
+    if (rc) return rc;
+    // debug flag bit 1: leave the partials unmerged (profiling the scan kernel alone)
+    if (D.n_merge > 0 && !(duo_get_debug_flags() & 2u)) {
+        CompressParams none{};
+        hipLaunchKernelGGL(duo_decode_post_kernel, dim3(4 * D.n_merge, D.n_batch), dim3(256), 0, st, D.M, 4 * D.n_merge, none);
+        DUO_HIP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 extern "C" int duo_attn_decode_bf16(const void *q, int64_t q_head_stride, void *out,
                                     int64_t out_head_stride, int32_t group,
                                     const duo_head_class *full, const duo_head_class *stream_cls,
@@ -1073,27 +915,6 @@ extern "C" int duo_attn_decode_batched_bf16(const void *q, int64_t q_batch_strid
     if (n_batch <= 0) return n_batch == 0 ? 0 : DUO_EINVAL;
     return attn_decode_impl(q, q_batch_stride, q_head_stride, out, out_batch_stride, out_head_stride, n_batch, group, full,
                             stream_cls, scale, head_dim, workspace, workspace_bytes, stream);
-}
-static int attn_decode_impl(const void *q, int64_t q_batch_stride, int64_t q_head_stride, void *out,
-                            int64_t out_batch_stride, int64_t out_head_stride, int32_t n_batch, int32_t group,
-                            const duo_head_class *full, const duo_head_class *stream_cls, float scale, int32_t head_dim,
-                            void *workspace, int64_t workspace_bytes, void *stream) {
-    if (head_dim != DUO_HEAD_DIM) return DUO_EHEADDIM;
-    if (q == nullptr || out == nullptr || group <= 0) return DUO_EINVAL;
-    DecodePlan D;
-    int rc = decode_plan(q, q_head_stride, out, out_head_stride, group, full, stream_cls, scale, workspace,
-                         workspace_bytes, D, n_batch, q_batch_stride, out_batch_stride);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc = decode_launch_split<false>(D, CompressParams{}, st);
-    if (rc) return rc;
-    // debug flag bit 1: leave the partials unmerged (profiling the split kernel alone)
-    if (D.n_merge > 0 && !(duo_get_debug_flags() & 2u)) {
-        CompressParams none{};
-        hipLaunchKernelGGL(duo_decode_post_kernel, dim3(4 * D.n_merge, D.n_batch), dim3(256), 0, st, D.M, 4 * D.n_merge, none);
-        DUO_HIP_CHECK_LAUNCH();
-    }
-    return 0;
 }
 
 // One decode step of one layer of the static dual-cache path in two launches: the split-KV scan of
@@ -1212,7 +1033,7 @@ static int decode_layer_impl(const duo_decode_layer_args *a, int32_t *new_stream
     if (one) {
         D.P.one_launch = 1;
         D.P.tickets = (int32_t *)tickets;
-        return decode_launch_split<true>(D, C, st);
+        return decode_launch_scan<true>(D, C, st);
     }
     // two launches: fold the streaming-pool update into the scan when every streaming head is one workgroup (grid.y == 1)
     static const bool fold_ok = [] { const char *e = getenv("DUO_DECODE_FOLD_COMPRESS"); return !e || atoi(e) != 0; }();
@@ -1221,7 +1042,7 @@ static int decode_layer_impl(const duo_decode_layer_args *a, int32_t *new_stream
         D.P.one_launch = 2;
         n_compress = 0;
     }
-    rc = decode_launch_split<true>(D, fold ? C : CompressParams{}, st);
+    rc = decode_launch_scan<true>(D, fold ? C : CompressParams{}, st);
     if (rc) return rc;
 
     // ---- launch 2: merge (+ streaming-pool update when it was not folded) ----------------------------
@@ -1230,6 +1051,16 @@ static int decode_layer_impl(const duo_decode_layer_args *a, int32_t *new_stream
         DUO_HIP_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// Device-side lengths: the values in the arguments only size the grid.  Planning lengths: at least one cached row per
+// class keeps the segment descriptors on the pools.
+static duo_decode_layer_args decode_planning_args(const duo_decode_layer_args &a) {
+    duo_decode_layer_args plan = a;
+    if (plan.full_len < 1) plan.full_len = 1;
+    if (plan.n_full > 0 && plan.full_len + 1 > plan.full_capacity) plan.full_len = plan.full_capacity - 1;
+    if (plan.str_len < 1) plan.str_len = 1;
+    return plan;
 }
 
 extern "C" int duo_decode_layer_bf16(const duo_decode_layer_args *a, int32_t *new_stream_len,
@@ -1253,11 +1084,7 @@ extern "C" int duo_decode_layer_batched_bf16(const duo_decode_layer_args *a, con
 extern "C" int duo_decode_layer_dev_bf16(const duo_decode_layer_args *a, const duo_decode_state *dev_state,
                                          void *workspace, int64_t workspace_bytes, void *stream) {
     if (!a || !dev_state) return DUO_EINVAL;
-    duo_decode_layer_args plan = *a;
-    // planning lengths: at least one cached row per class keeps the segment descriptors on the pools
-    if (plan.full_len < 1) plan.full_len = 1;
-    if (plan.n_full > 0 && plan.full_len + 1 > plan.full_capacity) plan.full_len = plan.full_capacity - 1;
-    if (plan.str_len < 1) plan.str_len = 1;
+    const duo_decode_layer_args plan = decode_planning_args(*a);
     return decode_layer_impl(&plan, nullptr, reinterpret_cast<const int32_t *>(dev_state), workspace, workspace_bytes,
                              nullptr, stream);
 }
@@ -1267,26 +1094,20 @@ extern "C" int duo_decode_layer_batched_dev_bf16(const duo_decode_layer_args *a,
                                                  const duo_decode_state *dev_state, void *workspace,
                                                  int64_t workspace_bytes, void *stream) {
     if (!a || !batch || !dev_state) return DUO_EINVAL;
-    duo_decode_layer_args plan = *a;
-    if (plan.full_len < 1) plan.full_len = 1;
-    if (plan.n_full > 0 && plan.full_len + 1 > plan.full_capacity) plan.full_len = plan.full_capacity - 1;
-    if (plan.str_len < 1) plan.str_len = 1;
+    const duo_decode_layer_args plan = decode_planning_args(*a);
     return decode_layer_impl(&plan, nullptr, reinterpret_cast<const int32_t *>(dev_state), workspace, workspace_bytes,
                              nullptr, stream, batch);
 }
 
 // The whole step in ONE launch: the split-KV scan as above, and behind an arrival ticket per kv head the last
-// workgroups to finish merge the partials and run the streaming pool's sink+recent update (see the end of
-// duo_decode_split_kernel).  dev_state == NULL: lengths from `a` (eager); else read on the device (graph replay).
+// workgroups to finish merge the partials and run the streaming pool's sink+recent update (see
+// duo_decode_tail.inc).  dev_state == NULL: lengths from `a` (eager); else read on the device (graph replay).
 extern "C" int duo_decode_step_bf16(const duo_decode_layer_args *a, int32_t *new_stream_len,
                                     const duo_decode_state *dev_state, void *workspace, int64_t workspace_bytes,
                                     void *tickets, void *stream) {
     if (!a || !tickets) return DUO_EINVAL;
     if (!dev_state) return decode_layer_impl(a, new_stream_len, nullptr, workspace, workspace_bytes, tickets, stream);
-    duo_decode_layer_args plan = *a;
-    if (plan.full_len < 1) plan.full_len = 1;
-    if (plan.n_full > 0 && plan.full_len + 1 > plan.full_capacity) plan.full_len = plan.full_capacity - 1;
-    if (plan.str_len < 1) plan.str_len = 1;
+    const duo_decode_layer_args plan = decode_planning_args(*a);
     return decode_layer_impl(&plan, new_stream_len, reinterpret_cast<const int32_t *>(dev_state), workspace,
                              workspace_bytes, tickets, stream);
 }

@@ -1,5 +1,5 @@
-// duo_decode_tail.inc — everything behind the scan loop, included textually at the end of both scan kernels
-// (duo_decode_split_kernel, duo_decode_scan_kernel) of duo_decode.hip.  Textual on purpose: handing the by-value kernel
+// duo_decode_tail.inc — everything behind the scan loop, included textually at the end of duo_decode_scan_kernel
+// (duo_decode.hip); kept as a file of its own so the kernel reads as prologue / loop / tail.  Textual on purpose: handing the by-value kernel
 // arguments P / CP to a helper by reference makes hipcc copy them to scratch (their dynamically indexed inv_freq tables
 // are then no longer read straight from the kernarg segment).
 // In scope: P, CP, GT, FUSED, m[], l[], acc[][], qh0, split, splits, ci, kvh, wave, sub, tg, and the batch row's bz,

@@ -283,7 +283,7 @@ __device__ __forceinline__ void dequant8_f32(uint32_t w, uint32_t sz2, float (&f
     }
 }
 
-// Same decomposition as duo_decode_split_kernel: 256-thread workgroup per (kv head, balanced token
+// Same decomposition as the bf16 scan (duo_decode_scan_kernel): 256-thread workgroup per (kv head, balanced token
 // chunk); 16 lanes per row — 4 packed bytes (8 dims) per lane, so one wave-load covers 4 rows = 256 B;
 // 16 tokens of K and V (+ their (scale, zero) words) in flight per wave.
 template <int GT>
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void duo_int4_decode_split_kernel(const Int4De
         }
     }
 
-    // ---- combine token groups, then waves (as duo_decode_split_kernel) ---------------------------
+    // ---- combine the wave's four token groups (cross-lane shuffles), then the four waves (LDS) ---
 #pragma unroll
     for (int g = 0; g < GT; ++g) {
         float mm = m[g];

@@ -122,15 +122,15 @@ const char *duo_error_string(int code);
  *        (slow, debugging aid for the transpose-read layout);
  * bit 1: decode skips the merge launch (output invalid; lets a profiler or a
  *        HIP-event pair bracket the split-KV kernel alone);
- * bit 2: decode K/V loads temporal instead of non-temporal;  bit 3: no register prefetch;
+ * bit 2: decode K/V loads temporal instead of non-temporal;  bit 3: unused;
  * bit 4: INT4 decode on the scalar-FMA kernel instead of the matrix-core one;
  * bit 5 / bit 6: INT4 / bf16 decode consume their loads without the arithmetic (output
  *        invalid: the memory-side ceiling of the launch);
  * bit 7: bf16 prefill stays on the 8-wave x 32-row kernel (the 4-wave x 64-row kernel is the default where it
  *        applies);  bit 8: no key-range split of the prefill launch;  bits 12-15 / bits 16-19: force that many key-range
  *        splits of the retrieval / the streaming class (capped by the workspace and the tile count);  bit 21: the prefill
- *        kernel's first bulk run stops at the end of segment A instead of chaining into segment B (the round-1..5 form);  bit 9: decode scan on the long-prologue kernel
- *        (duo_decode_split_kernel) instead of the short-prologue one;  bit 10: prefill in the plain q-tile-major block
+ *        kernel's first bulk run stops at the end of segment A instead of chaining into segment B (the round-1..5 form);  bit 9: every decode scan on the wide-argument
+ *        form of duo_decode_scan_kernel (otherwise taken only when a field does not fit the packed arguments);  bit 10: prefill in the plain q-tile-major block
  *        order instead of the XCD-aware one;  bit 11: INT4 decode on the dequantising kernel whatever `fused` asks for.
  *        Measurement / test aids only. */
 void duo_set_debug_flags(uint32_t flags);

@@ -149,11 +149,11 @@ def _run_bf16_attention(call, group, nf, ns, S, lenF, lenS, head_major, what, se
 DECODE_LENS = [1, 63, 64, 65, 257, 5000]
 
 
-@pytest.mark.parametrize("flags", [0, 512], ids=["scan", "long-prologue"])
+@pytest.mark.parametrize("flags", [0, 512], ids=["scan", "wide"])
 @pytest.mark.parametrize("group", [4, 1, 3])
 @pytest.mark.parametrize("head_major", [True, False])
 def test_bf16_decode(head_major, group, flags):
-    """attn_decode over both head classes; 5000 rows are split over workgroups; debug bit 9 = duo_decode_split_kernel"""
+    """attn_decode over both head classes; 5000 rows are split over workgroups; debug bit 9 = the scan kernel's wide-argument form"""
     h = _hip()
     with _Flags(flags):
         for L in DECODE_LENS:

@@ -233,12 +233,35 @@ FUSED_CASES = [
 ]
 
 
+@pytest.fixture
+def wide_scan():
+    """debug bit 9: every decode scan runs the wide-argument form of duo_decode_scan_kernel"""
+    h = _hip()
+    h.set_debug_flags(512)
+    try:
+        yield 512
+    finally:
+        h.set_debug_flags(0)
+
+
 @pytest.mark.parametrize("two_launch", [False, True])
 @pytest.mark.parametrize("case", FUSED_CASES)
 def test_decode_layer_fused(case, two_launch):
     """duo_decode_step_bf16 (ONE launch: scan with RoPE + retrieval append folded in, merge + streaming update
     behind per-head arrival tickets) and duo_decode_layer_bf16 (the same as two launches) against the oracle's
     step-by-step restatement of llama.py:332-425 for q_len == 1."""
+    _check_decode_layer_fused(case, two_launch)
+
+
+@pytest.mark.parametrize("two_launch", [False, True])
+@pytest.mark.parametrize("case", FUSED_CASES)
+def test_decode_layer_fused_on_the_wide_form(case, two_launch, wide_scan):
+    """the same step, same assertions, on the scan kernel's wide-argument form (RoPE, the retrieval append, the tickets and
+    the folded streaming-pool update of the form that takes launches whose fields do not fit the packed arguments)"""
+    _check_decode_layer_fused(case, two_launch)
+
+
+def _check_decode_layer_fused(case, two_launch):
     from oracle.duo_oracle import OracleBackend
 
     group, nf, ns, full_len, str_len, sink, recent, pos = case
@@ -857,24 +880,143 @@ def test_row_blocks_equal_whole_chunk_on_gpu():
             assert torch.equal(x[l][:, :ln], y[l][:, :ln])
 
 
-# ----------------------------------------------------------------------------- the fallback scan kernel stays tested
+# ----------------------------------------------------------------------------- the scan kernel's wide-argument form
 @pytest.mark.parametrize("case", [DECODE_CASES[2], DECODE_CASES[5], DECODE_CASES[8], DECODE_CASES[10], DECODE_CASES[12]])
-def test_decode_on_the_long_prologue_scan_kernel(case):
-    """duo_decode_split_kernel (round 2's scan) is what a launch falls back to when a stride does not fit the packed
-    argument fields of duo_decode_scan_kernel; debug bit 9 selects it for any launch."""
-    h = _hip()
+def test_decode_on_the_wide_form(case, wide_scan):
+    """The wide-argument form of duo_decode_scan_kernel is what a launch takes when a field does not fit the packed
+    arguments; debug bit 9 selects it for any launch."""
     group, nf, ns, n_full, n_stream = case
-    h.set_debug_flags(512)
+    out, ref, bud = _attention_case(1, group, nf, ns, n_full, n_stream, True, seed=hash(case) % 1000 + 1)
+    attn_close(out, ref, f"decode (wide form) {case}", bud)
+
+
+def _assert_both_scan_forms_agree(run, what):
+    """``run()`` -> tuple of CPU tensors / ints, once with the packed form (flags 0) and once with the wide form (bit 9):
+    the same partition and the same source run in both, so every result must be bit-identical."""
+    h = _hip()
+    res = []
     try:
-        out, ref, bud = _attention_case(1, group, nf, ns, n_full, n_stream, True, seed=hash(case) % 1000 + 1)
+        for flags in (0, 512):
+            h.set_debug_flags(flags)
+            res.append(run())
+            torch.cuda.synchronize()
     finally:
         h.set_debug_flags(0)
-    attn_close(out, ref, f"decode (long-prologue kernel) {case}", bud)
+    assert len(res[0]) == len(res[1])
+    for i, (a, b) in enumerate(zip(*res)):
+        if torch.is_tensor(a):
+            assert torch.isfinite(a.float()).all(), f"{what}: result {i} of the packed form is not finite"
+            assert torch.equal(a, b), f"{what}: result {i} differs in {int((a != b).sum())} of {a.numel()} elements"
+        else:
+            assert a == b, f"{what}: result {i}: {a} != {b}"
+
+
+@pytest.mark.parametrize("case", [(4, 1, 1, 1, 1), (4, 2, 6, 17, 5), (4, 0, 8, 0, 383), (3, 2, 2, 515, 30), (8, 1, 1, 2049, 50)])
+def test_packed_and_wide_forms_agree_attn_decode(case):
+    """one cached row; a partial 16-token group; no retrieval class; GT 1 with several splits; grid.y = 2"""
+    h = _hip()
+    group, nf, ns, n_full, n_stream = case
+    g = torch.Generator().manual_seed(sum(case))
+    Hq = (nf + ns) * group
+    q = _rand((Hq, D), g).to(DEV)
+    kn, vn = _rand((1, nf + ns, D), g).to(DEV), _rand((1, nf + ns, D), g).to(DEV)
+    cls, keep = [], []       # (the descriptors hold raw pointers: `keep` keeps the pools alive)
+    for lo, n_h, L in ((0, nf, n_full), (nf, ns, n_stream)):
+        if n_h == 0:
+            cls.append(None)
+            continue
+        _, _, pk, pv = _make_pool(L, n_h, g, True)
+        keep += [pk, pv]
+        cls.append(h.make_class(n_h, lo * group, h.make_seg(pk, pv), h.make_seg(kn[:, lo:lo + n_h], vn[:, lo:lo + n_h])))
+
+    def run():
+        out = torch.full((Hq, D), float("nan"), dtype=torch.bfloat16, device=DEV)
+        h.attn_decode(q, out, group, cls[0], cls[1], D ** -0.5)
+        return (out.cpu(),)
+
+    _assert_both_scan_forms_agree(run, f"attn_decode {case}")
+
+
+def _fused_step_inputs(group, nf, ns, full_len, str_len, sink, recent, cap, seed, batch=None):
+    """CPU tensors of one fused decode step: q, k, v, then the head-major pools full_k, full_v, str_k, str_v with rows
+    [0, full_len) / [0, str_len) random and the rest zero; ``batch`` = B prepends a batch dimension to all of them"""
+    g = torch.Generator().manual_seed(seed)
+    nkv, W, B = nf + ns, sink + recent, ([batch] if batch else [])
+    acts = [_rand((*B, n, D), g) for n in ((nf + ns) * group, nkv, nkv)]
+    pools = []
+    for n_h, rows, live in ((nf, cap, full_len), (nf, cap, full_len), (ns, W, str_len), (ns, W, str_len)):
+        t = torch.zeros(*B, max(n_h, 1), rows, D, dtype=torch.bfloat16)
+        t[..., :live, :] = _rand((*B, max(n_h, 1), live, D), g)
+        pools.append(t)
+    return acts, pools
+
+
+def _pool_views(pools, nf, ns):
+    """fresh device copies of the head-major pools as [.., T, h, D] views of the class's heads"""
+    dev = [t.to(DEV).transpose(-3, -2) for t in pools]
+    return [t[..., :n_h, :] for t, n_h in zip(dev, (nf, nf, ns, ns))]
+
+
+@pytest.mark.parametrize("two_launch", [False, True])
+@pytest.mark.parametrize("case", [(2, 2, 2, 0, 0, 4, 8, 0), (4, 4, 4, 1000, 384, 128, 256, 1000)])
+def test_packed_and_wide_forms_agree_decode_layer(case, two_launch):
+    """empty pools; the usual two-class step — output, all four pools and the returned streaming length"""
+    h = _hip()
+    group, nf, ns, full_len, str_len, sink, recent, pos = case
+    (q, k, v), pools = _fused_step_inputs(group, nf, ns, full_len, str_len, sink, recent, full_len + 3, seed=full_len + 1)
+    qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
+
+    def run():
+        pv = _pool_views(pools, nf, ns)
+        out = torch.full(q.shape, float("nan"), dtype=torch.bfloat16, device=DEV)
+        n = h.decode_layer(qd, kd, vd, out, nf, pv[0], pv[1], full_len, pv[2], pv[3], str_len, sink, recent, pos, 1.0, 5e5,
+                           D ** -0.5, two_launch=two_launch)
+        return (out.cpu(), n) + tuple(t.cpu() for t in pv)
+
+    _assert_both_scan_forms_agree(run, f"decode_layer {case} two_launch={two_launch}")
+    assert int(h.decode_tickets(torch.device(DEV)).abs().sum()) == 0
+
+
+@pytest.mark.parametrize("two_launch", [False, True])
+def test_packed_and_wide_forms_agree_decode_layer_dev(two_launch):
+    """device-side lengths (300 retrieval rows, 12 streaming rows) under a grid planned for 700 rows: one bucket above"""
+    h = _hip()
+    group, nf, ns, full_len, str_len, plan, sink, recent = 4, 2, 2, 300, 12, 700, 4, 8
+    (q, k, v), pools = _fused_step_inputs(group, nf, ns, full_len, str_len, sink, recent, plan + 1, seed=312)
+    qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
+    st = torch.tensor([full_len, str_len, full_len, 0], dtype=torch.int32, device=DEV)
+
+    def run():
+        pv = _pool_views(pools, nf, ns)
+        out = torch.full(q.shape, float("nan"), dtype=torch.bfloat16, device=DEV)
+        h.decode_layer_dev(qd, kd, vd, out, nf, pv[0], pv[1], plan, pv[2], pv[3], str_len, sink, recent, full_len, 1.0, 5e5,
+                           D ** -0.5, st, two_launch=two_launch)
+        return (out.cpu(),) + tuple(t.cpu() for t in pv)
+
+    _assert_both_scan_forms_agree(run, f"decode_layer_dev two_launch={two_launch}")
+    assert int(h.decode_tickets(torch.device(DEV)).abs().sum()) == 0
+
+
+def test_packed_and_wide_forms_agree_decode_layer_batched():
+    """two batch rows at one position in one launch pair (grid.z = 2)"""
+    h = _hip()
+    group, nf, ns, full_len, str_len, sink, recent = 4, 2, 2, 515, 12, 4, 8
+    (q, k, v), pools = _fused_step_inputs(group, nf, ns, full_len, str_len, sink, recent, full_len + 3, seed=99, batch=2)
+    qd, kd, vd = q.to(DEV), k.to(DEV), v.to(DEV)
+
+    def run():
+        pv = _pool_views(pools, nf, ns)
+        out = torch.full(q.shape, float("nan"), dtype=torch.bfloat16, device=DEV)
+        n = h.decode_layer_batched(qd, kd, vd, out, nf, pv[0], pv[1], full_len, pv[2], pv[3], str_len, sink, recent, full_len,
+                                   1.0, 5e5, D ** -0.5)
+        return (out.cpu(), n) + tuple(t.cpu() for t in pv)
+
+    _assert_both_scan_forms_agree(run, "decode_layer_batched")
 
 
 def test_decode_falls_back_when_a_stride_does_not_fit_the_packed_fields():
-    """q rows 70 000 elements apart (> 16 bits): the launcher must take the general kernel, with the same result as the
-    short-prologue kernel on a compact copy of the same q."""
+    """q rows 70 000 elements apart (> 16 bits): the launcher must take the wide-argument form of the scan kernel, with the
+    same result as the packed form on a compact copy of the same q."""
     from duo_attn.backend import HipBackend
 
     g = torch.Generator().manual_seed(77)
@@ -896,5 +1038,5 @@ def test_decode_falls_back_when_a_stride_does_not_fit_the_packed_fields():
         be.attention(q, out, group, full, stream, D ** -0.5)
         outs.append(out)
     assert torch.isfinite(outs[0].float()).all()
-    # same partition, same arithmetic per workgroup up to the fold order of the epilogue (shared): equal to the bf16 ulp
-    assert (outs[0].float() - outs[1].float()).abs().max() <= 2.0 ** -7 * outs[1].float().abs().max()
+    # same partition, same source in both forms: bit-identical
+    assert torch.equal(outs[0], outs[1])

@@ -8,7 +8,7 @@ import torch
 from duo_attn import _hip
 
 nf = int(sys.argv[1]) if len(sys.argv) > 1 else 4
-flags = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # 512: the long-prologue scan kernel
+flags = int(sys.argv[2]) if len(sys.argv) > 2 else 0      # 512: the scan kernel's wide-argument form
 HQ, HKV, D, N, W = 32, 8, 128, 131072, 384
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev).manual_seed(0)
