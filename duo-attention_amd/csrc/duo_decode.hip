@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "duo_kv_ops.h"
+#include "duo_decode_plan.h"
 
 namespace {
 
@@ -680,7 +681,7 @@ extern "C" int64_t duo_attn_decode_workspace_bytes(int32_t n_q_heads, int32_t ma
     return (int64_t)n_q_heads * max_splits * (DUO_HEAD_DIM + 2) * (int64_t)sizeof(float);
 }
 
-static int decode_target_wgs() {
+int duo_decode_target_wgs() {
     // workgroups the scan kernel aims for across both classes (tuning knob, read once)
     static int v = [] {
         const char *e = getenv("DUO_DECODE_TARGET_WGS");
@@ -708,7 +709,7 @@ static int plan_bucket_units(int L) {
 }
 extern "C" int32_t duo_decode_plan_bucket(int32_t n_tokens) { return n_tokens <= 0 ? 0 : plan_bucket_units(n_tokens); }
 
-static void choose_splits(int n_kv_heads, int L, int max_splits, int budget_wgs, int &splits) {
+void duo_decode_choose_splits(int n_kv_heads, int L, int max_splits, int budget_wgs, int &splits) {
     if (n_kv_heads <= 0 || L <= 0) {
         splits = 0;
         return;
@@ -779,13 +780,13 @@ static int decode_plan(const void *q, int64_t q_head_stride, void *out, int64_t 
     const int64_t per_split = (int64_t)n_q_heads * (DUO_HEAD_DIM + 2) * (int64_t)sizeof(float) * n_batch;   // every batch row has its own partials
     const int max_splits = workspace ? (int)std::min<int64_t>(workspace_bytes / per_split, 1024) : 0;
     {
-        const int target = std::max(1, decode_target_wgs() / n_batch);     // one resident round over all rows
+        const int target = std::max(1, duo_decode_target_wgs() / n_batch);     // one resident round over all rows
         const int ms = max_splits > 0 ? max_splits : 1;
         const int Ls = P.cls[1].a.len + P.cls[1].b.len, Lf = P.cls[0].a.len + P.cls[0].b.len;
         // the streaming class is a few hundred rows per head: one workgroup each unless it is alone
-        choose_splits(P.cls[1].n_kv_heads, Ls, ms, P.cls[0].n_kv_heads > 0 ? P.cls[1].n_kv_heads : target, P.splits[1]);
+        duo_decode_choose_splits(P.cls[1].n_kv_heads, Ls, ms, P.cls[0].n_kv_heads > 0 ? P.cls[1].n_kv_heads : target, P.splits[1]);
         const int used = P.cls[1].n_kv_heads * P.splits[1];
-        choose_splits(P.cls[0].n_kv_heads, Lf, ms, std::max(target - used, P.cls[0].n_kv_heads), P.splits[0]);
+        duo_decode_choose_splits(P.cls[0].n_kv_heads, Lf, ms, std::max(target - used, P.cls[0].n_kv_heads), P.splits[0]);
         P.chunk[0] = P.chunk[1] = 0;
     }
     const int need = std::max(P.splits[0], P.splits[1]);

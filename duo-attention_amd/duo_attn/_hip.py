@@ -277,6 +277,17 @@ _SIGNATURES = {
         [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,
          POINTER(Int4Pool), POINTER(Int4Pool), c_float, c_int32, c_int32, c_void_p, c_int64, c_void_p],
     ),
+    "duo_attn_decode_multi_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "duo_attn_decode_multi_bf16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, POINTER(HeadClass), POINTER(HeadClass),
+         c_float, c_int32, c_void_p, c_int64, c_void_p],
+    ),
+    "duo_attn_decode_multi_batched_bf16": (
+        ctypes.c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,
+         POINTER(HeadClass), POINTER(HeadClass), c_float, c_int32, c_void_p, c_int64, c_void_p],
+    ),
     "duo_lambda_attn_fwd_bf16": (
         ctypes.c_int,
         [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
@@ -646,6 +657,64 @@ def attn_decode(q: torch.Tensor, out: torch.Tensor, group: int, full: Optional[H
             float(scale), q.shape[1], ws.data_ptr(), ws.numel() * 4, _stream_ptr(),
         ),
         "duo_attn_decode_bf16",
+    )
+
+
+_MULTI_MAX_SPLITS = 256      # DUO_DECODE_MULTI_MAX_SPLITS: the most splits per kv head a multi-token step's plan asks for
+
+
+def decode_multi_workspace(device: torch.device, n_q_heads: int, n_tokens: int) -> torch.Tensor:
+    """fp32 scratch for the partials of a multi-token step ([token][q head][split][2 + 128]): like ``decode_workspace`` one
+    buffer per (device, stream, size), never replaced or freed; the token count is rounded up to a power of two so that a
+    q-head count owns at most seven sizes."""
+    scope = _active_scope()
+    cache = _workspaces if scope is None else scope
+    rows = 1 << max(0, int(n_tokens) - 1).bit_length()
+    key = _stream_key(device) + ("multi", int(n_q_heads), rows)
+    ws = cache.get(key)
+    if ws is None:
+        need = load_library().duo_attn_decode_multi_workspace_bytes(int(n_q_heads), rows, _MULTI_MAX_SPLITS)
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        cache[key] = ws
+    return ws
+
+
+def attn_decode_multi(q: torch.Tensor, out: torch.Tensor, group: int, full: Optional[HeadClass],
+                      stream: Optional[HeadClass], scale: float):
+    """q, out: [T, Hq, D] bf16 views, 1 <= T <= 64: the attention of a T-token decode step as a split-KV stream over both head
+    classes (segB of each class = the step's T rows, causal).  ``group`` must be 1, 2, 4, 8 or 16."""
+    lib = load_library()
+    _require_gpu_bf16(q, "q")
+    _require_gpu_bf16(out, "out")
+    assert q.dim() == 3 and out.shape == q.shape
+    ws = decode_multi_workspace(q.device, q.shape[1], q.shape[0])
+    _check(
+        lib.duo_attn_decode_multi_bf16(
+            q.data_ptr(), q.stride(0), q.stride(1), out.data_ptr(), out.stride(0), out.stride(1), q.shape[0], int(group),
+            byref(full) if full is not None else None, byref(stream) if stream is not None else None,
+            float(scale), q.shape[2], ws.data_ptr(), ws.numel() * 4, _stream_ptr(),
+        ),
+        "duo_attn_decode_multi_bf16",
+    )
+
+
+def attn_decode_multi_batched(q: torch.Tensor, out: torch.Tensor, group: int, full: Optional[HeadClass],
+                              stream: Optional[HeadClass], scale: float):
+    """q, out: [B, T, Hq, D] bf16 views; the classes' segments were built from [B, rows, h, D] views (``make_seg``): every
+    batch row of the T-token step in one launch pair."""
+    lib = load_library()
+    _require_gpu_bf16(q, "q")
+    _require_gpu_bf16(out, "out")
+    assert q.dim() == 4 and out.shape == q.shape
+    ws = decode_multi_workspace(q.device, q.shape[0] * q.shape[2], q.shape[1])
+    _check(
+        lib.duo_attn_decode_multi_batched_bf16(
+            q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), out.data_ptr(), out.stride(0), out.stride(1),
+            out.stride(2), q.shape[0], q.shape[1], int(group), byref(full) if full is not None else None,
+            byref(stream) if stream is not None else None, float(scale), q.shape[3], ws.data_ptr(), ws.numel() * 4,
+            _stream_ptr(),
+        ),
+        "duo_attn_decode_multi_batched_bf16",
     )
 
 

@@ -64,6 +64,14 @@ class HipBackend:
             #  block of the MFMA kernel)
             self._hip.attn_prefill(q, out, group, fc, sc, scale)
 
+    # -- the same calls for a decode step of a few tokens (1 < q_len <= 64, bf16, segB = the step's rows): the split-KV
+    #    matrix-core stream instead of the prefill kernel's 256-row query tiles (opt-in: multi_token_decode=True)
+    def attention_multi(self, q, out, group: int, full: ClassDesc, stream: ClassDesc, scale: float):
+        self._hip.attn_decode_multi(q, out, group, self._cls(full), self._cls(stream), scale)
+
+    def attention_multi_batched(self, q, out, group: int, full: ClassDesc, stream: ClassDesc, scale: float):
+        self._hip.attn_decode_multi_batched(q, out, group, self._cls(full), self._cls(stream), scale)
+
     # -- batched forms: the batch row is a grid dimension of the same kernels (one launch for all rows).  Views carry a
     #    leading batch dimension: q/out [B, S, Hq, D], segments [B, T, h, D]
     def attention_batched(self, q, out, group: int, full: ClassDesc, stream: ClassDesc, scale: float):

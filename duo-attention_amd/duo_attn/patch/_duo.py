@@ -63,6 +63,19 @@ def first_positions(position_ids):
     return int(first[0]) if all(f == first[0] for f in first) else [int(f) for f in first]
 
 
+# Longest decode step the multi-token route takes (``DuoAttentionStaticKVCache(multi_token_decode=True)``): the largest power of
+# two T at which the split-KV stream beats the prefill kernel on the same step at 131072 cached rows — the table is in
+# profiles/bf16_multi_token.md.
+MULTI_TOKEN_LIMIT = 16
+MULTI_TOKEN_GROUPS = (1, 2, 4, 8, 16)       # 16 / group tokens fill the 16 q columns of the kernel's fragments
+
+
+def multi_token_route(kv_cache, past: int, q_len: int, dtype, groups: int) -> bool:
+    """whether a step's attention takes ``attention_multi`` (duo_decode_multi_kernel) instead of the prefill kernel"""
+    return (bool(getattr(kv_cache, "multi_token_decode", False)) and past > 0 and 1 < q_len <= MULTI_TOKEN_LIMIT
+            and dtype == torch.bfloat16 and groups in MULTI_TOKEN_GROUPS)
+
+
 def duo_static_attention_core(query_states, key_states, value_states, kv_cache, layer_idx, pos0,
                               rope_scale, rope_theta):
     """The hot path proper: everything between the q/k/v projections and o_proj in reference
@@ -105,16 +118,19 @@ def duo_static_attention_core(query_states, key_states, value_states, kv_cache, 
         ns = num_kv - nf
         pk, pv = kv_cache.full_key_states_list[layer_idx], kv_cache.full_value_states_list[layer_idx]
         ck, cv = kv_cache.get_streaming_kv(layer_idx)
+        # a step of a few tokens (opt-in): the same two classes on the split-KV stream; only this launch differs
+        multi = multi_token_route(kv_cache, past, q_len, query_states.dtype, groups)
+        attention = be.attention_multi if multi else be.attention
         if batched:
             full = (nf, 0, (pk[:, :past_l], pv[:, :past_l]),
                     (pk[:, past_l:past_l + q_len], pv[:, past_l:past_l + q_len])) if nf > 0 else None
             stream = (ns, nf * groups, (ck, cv), (sk, sv)) if ns > 0 else None
-            be.attention_batched(query_states, attn_output, groups, full, stream, scale)
+            (be.attention_multi_batched if multi else be.attention_batched)(query_states, attn_output, groups, full, stream, scale)
         for b in range(0 if batched else bsz):
             full = (nf, 0, (pk[b, :past_l], pv[b, :past_l]),
                     (pk[b, past_l:past_l + q_len], pv[b, past_l:past_l + q_len])) if nf > 0 else None
             stream = (ns, nf * groups, (ck[b], cv[b]), (sk[b], sv[b])) if ns > 0 else None
-            be.attention(query_states[b], attn_output[b], groups, full, stream, scale)
+            attention(query_states[b], attn_output[b], groups, full, stream, scale)
 
     kv_cache.update_streaming_kv(layer_idx, sk, sv)
     return attn_output

@@ -18,6 +18,7 @@ MI355X-first differences that do not change the interface:
 """
 from __future__ import annotations
 
+import functools
 import types
 from typing import Optional
 
@@ -27,9 +28,25 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from ..backend import get_backend
 
 
-class DuoAttentionStaticKVCache:
-    """Same constructor, attributes and methods as reference static_kv_cache.py:18-315."""
+def _takes_port_options(init):
+    """``__init__`` keeps the reference's signature, to introspection too (the API test pins its parameter list); what this
+    port adds is keyword-only and taken off before it runs:
+    ``multi_token_decode`` (default False): decode steps of 2 .. MULTI_TOKEN_LIMIT tokens run their attention on the split-KV
+    matrix-core stream (duo_decode_multi_kernel) instead of the prefill kernel (``_duo.multi_token_route``)."""
 
+    @functools.wraps(init)
+    def wrapper(self, *args, multi_token_decode: bool = False, **kwargs):
+        self.multi_token_decode = bool(multi_token_decode)
+        init(self, *args, **kwargs)
+
+    return wrapper
+
+
+class DuoAttentionStaticKVCache:
+    """Same constructor, attributes and methods as reference static_kv_cache.py:18-315 (+ the keyword-only
+    ``multi_token_decode`` option, see ``_takes_port_options``)."""
+
+    @_takes_port_options
     def __init__(self, model, full_attention_heads, batch_size, max_size, sink_size, recent_size):
         self.batch_size = batch_size
         self.max_size = max_size

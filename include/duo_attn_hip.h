@@ -57,6 +57,8 @@
  *   duo_lambda_attn_bwd_workspace_bytes — the Λ-mask (streaming) attention of retrieval-head training, with its backward.
  * ABI version 8 (additions only, no signature changed): + duo_attn_decode_int4_multi_f16, duo_attn_decode_int4_multi_batched_f16
  *   — a step of 2..64 query tokens against non-empty INT4 pools, computed on the packed pools.
+ *   Added later under the same version (additions only, nothing a v8 caller binds changed): duo_attn_decode_multi_workspace_bytes,
+ *   duo_attn_decode_multi_bf16, duo_attn_decode_multi_batched_bf16 — the same kind of step over the bf16 pools.
  *
  * Attention semantics (flash-attn 2.6.3 flash_attn_func, causal=True,
  * bottom-right aligned): a query at row i of the S new rows sees every key of
@@ -492,6 +494,34 @@ int duo_attn_decode_int4_multi_batched_f16(const void *q, int64_t q_batch_stride
                                            const duo_int4_pool *full, const duo_int4_pool *stream_cls, float scale,
                                            int32_t head_dim, int32_t fused, void *workspace, int64_t workspace_bytes,
                                            void *stream);
+
+/* ---- a decode step of n_tokens (1..64) bf16 query tokens over the bf16 pools (a later addition to ABI version 8) ----
+ * llama.py:374-421 with q_len = n_tokens after a prefill: the attention of a speculative-decoding verify step, a short chat
+ * turn, the ragged tail of a chunked prefill — as a split-KV stream over each kv head's rows (duo_decode_multi_kernel, both
+ * products on v_mfma_f32_16x16x32_bf16) instead of the prefill kernel's 256-row query tiles.  Head classes as for the prefill
+ * entry points: segA entirely visible, segB = the step's n_tokens rows, causally (token i sees segB row j iff j <= i);
+ * segB.len must equal n_tokens (row blocks of a longer chunk stay with duo_attn_prefill_*), else DUO_EINVAL.  q / out
+ * [n_tokens, n_q_heads, 128] bf16, strides in elements (q and every K/V stride: multiples of 8, out: of 4).  16 / group tokens
+ * share one pass over a kv head's rows; group must be 1, 2, 4, 8 or 16 (DUO_EGROUP).  fp32 softmax, P rounded to bf16 before
+ * P.V, bf16 output; no atomics: repeated calls are bit-equal.  Partials: fp32 [token][q head][split][2 + 128];
+ * duo_attn_decode_multi_workspace_bytes() is the size for a given split count of one batch row.  The split plan is the
+ * single-token one (duo_decode_plan_bucket, 256 workgroups) with the workgroups shared by the column blocks, at most
+ * DUO_DECODE_MULTI_MAX_SPLITS per kv head, and does not depend on the workspace: one that cannot hold the plan's splits is
+ * DUO_EWORKSPC; the size for DUO_DECODE_MULTI_MAX_SPLITS always holds it.  Every argument error returns before any launch.
+ * n_tokens == 1 is duo_attn_decode_bf16 (any group it takes), bit for bit.                                                 */
+#define DUO_DECODE_MULTI_MAX_SPLITS 256
+int64_t duo_attn_decode_multi_workspace_bytes(int32_t n_q_heads, int32_t n_tokens, int32_t max_splits);
+int duo_attn_decode_multi_bf16(const void *q, int64_t q_token_stride, int64_t q_head_stride, void *out,
+                               int64_t out_token_stride, int64_t out_head_stride, int32_t n_tokens, int32_t group,
+                               const duo_head_class *full, const duo_head_class *stream_cls, float scale, int32_t head_dim,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+/* the same for every batch row in one launch: q / out [B, n_tokens, n_q_heads, 128], the segments carry their batch strides,
+ * grid.z = batch row; n_batch * n_tokens <= 65535.  The un-batched form is its n_batch = 1 case.                          */
+int duo_attn_decode_multi_batched_bf16(const void *q, int64_t q_batch_stride, int64_t q_token_stride, int64_t q_head_stride,
+                                       void *out, int64_t out_batch_stride, int64_t out_token_stride, int64_t out_head_stride,
+                                       int32_t n_batch, int32_t n_tokens, int32_t group, const duo_head_class *full,
+                                       const duo_head_class *stream_cls, float scale, int32_t head_dim, void *workspace,
+                                       int64_t workspace_bytes, void *stream);
 
 /* ---- RMSNorm: y = x * rsqrt(mean(x^2) + eps) * w, rows of `hidden` bf16 ---- */
 int duo_rmsnorm_bf16(const void *x, const void *w, void *y, int64_t n_rows,

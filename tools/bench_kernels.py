@@ -5,6 +5,8 @@
     python tools/bench_kernels.py decode  --ctx 131072 --reps 20        # all 32 layers of the bench pattern
     python tools/bench_kernels.py decode_int4 --ctx 1048576 --q-len 2 4 16   # one layer: a T-token step on the packed pools
                                                                         # against get() + fp16 prefill and the 1-token decode
+    python tools/bench_kernels.py decode --ctx 131072 --nf 4 --q-len 1 2 4 8 16 32 64     # one layer: a T-token step on the bf16 pools,
+                                                                        # split-KV stream vs the prefill kernel vs the 1-token decode
 Prints one JSON line per case: avg ms, algorithmic TFLOP/s or GB/s.
 """
 import argparse
@@ -102,6 +104,59 @@ def int4_multi_token(a, dev, g):
                           "parent_scratch_MB": round(sum(b.numel() for b in kv._scratch.values()) * 2 / 1e6, 1)}), flush=True)
 
 
+def bf16_multi_token(a, be, dev, g):
+    """One layer of the bf16 dual cache (--nf retrieval + 8 - nf streaming kv heads, group 4, a full 384-row streaming window)
+    whose retrieval pool holds --ctx rows, the step's T rows included.  Per T, alternating in this process after a warm-up of
+    each:
+      single  attention (T = 1)    the existing one-token split-KV scan (the yardstick for a one-pass step)
+      multi   attention_multi      the T-token step on the split-KV matrix-core stream (duo_decode_multi_kernel)
+      parent  attention            the same step on the prefill kernel — the route every q_len > 1 took before
+    Prints one JSON line per T: median / min / max ms of each and the ratios of the medians."""
+    N, G, scale = a.ctx, HQ // HKV, D ** -0.5
+    nf, ns = a.nf, HKV - a.nf
+    fk, fv = pools(max(nf, 1), N, dev, g)
+    sk, sv = pools(max(ns, 1), W, dev, g)
+
+    def timed(fn):
+        x, y = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        x.record()
+        fn()
+        y.record()
+        return x, y
+
+    def classes(T, kn, vn):
+        full = (nf, 0, (fk[:N - T, :nf], fv[:N - T, :nf]), (fk[N - T:N, :nf], fv[N - T:N, :nf])) if nf else None
+        stream = (ns, nf * G, (sk[:, :ns], sv[:, :ns]), (kn[:T, nf:], vn[:T, nf:])) if ns else None
+        return full, stream
+
+    for T in a.q_len:
+        q = torch.randn(T, HQ, D, generator=g, device=dev).to(torch.bfloat16)
+        kn, vn = pools(HKV, T, dev, g)
+        out = torch.empty_like(q)
+        one, many = classes(1, kn, vn), classes(T, kn, vn)
+        routes = {"single": lambda: be.attention(q[:1], out[:1], G, *one, scale),
+                  "multi": lambda: be.attention_multi(q, out, G, *many, scale),
+                  "parent": lambda: be.attention(q, out, G, *many, scale)}
+        if T == 1:
+            routes["parent"] = routes["single"]     # (a one-token step never took the prefill kernel)
+        for fn in routes.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        evs = {name: [] for name in routes}
+        for _ in range(max(a.reps, 5)):
+            for name, fn in routes.items():
+                evs[name].append(timed(fn))
+        torch.cuda.synchronize()
+        ms = {name: sorted(x.elapsed_time(y) for x, y in e) for name, e in evs.items()}
+        med = {name: t[len(t) // 2] for name, t in ms.items()}
+        print(json.dumps({"case": f"bf16 step ctx={N} nf={nf} T={T}",
+                          **{f"{name}_ms": {"median": round(med[name], 4), "min": round(t[0], 4), "max": round(t[-1], 4)}
+                             for name, t in ms.items()},
+                          "multi_over_single": round(med["multi"] / med["single"], 3),
+                          "parent_over_multi": round(med["parent"] / med["multi"], 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["prefill", "decode", "decode_int4", "linear"])
@@ -114,7 +169,7 @@ def main():
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--uniform-nf", type=int, default=-1, help="decode: every layer has this many retrieval kv heads")
     ap.add_argument("--q-len", type=int, nargs="+", default=None,
-                    help="decode_int4: time a step of T tokens (one layer, --nf retrieval kv heads, --ctx rows) three ways")
+                    help="decode / decode_int4: time a step of T tokens (one layer, --nf retrieval kv heads, --ctx rows) three ways")
     a = ap.parse_args()
     from duo_attn import _hip
     from duo_attn.backend import get_backend
@@ -179,6 +234,8 @@ def main():
                           "tflops_avg": flops / avg / 1e9, "tflops_best": flops / mn / 1e9}))
     elif a.what == "decode_int4" and a.q_len:
         int4_multi_token(a, dev, g)
+    elif a.what == "decode" and a.q_len:
+        bf16_multi_token(a, be, dev, g)
     elif a.what == "decode_int4":
         import bench
 
